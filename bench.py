@@ -9,6 +9,14 @@ the reference times as train/steps_per_second (rl_algo_impls/ppo/ppo.py:221,422-
     python bench.py [--gpus N --steps K --warmup W]   (N > 1: the N ranks are started here unless a
                                                        launcher such as torch.distributed.run already did) [--config cartpole|pong|halfcheetah|microrts]
                     [--batch-policy yaml|scaled] [--env-partition split|per-rank] [--dp-batch global|per-rank]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up and K timed steps, writes the last timed step's outputs when
+--dump-outputs is given and prints the JSON line: `value`, `ms_per_step` and the dominant kernel's
+`roofline` / `roofline_latency`, which are read off the timed steps themselves.  --full adds the
+measurements that take runs of their own after the timed steps: the GAE kernel's rooflines
+(`roofline_gae`, `roofline_gae_bandwidth_regime`) and, for the CartPole config, the CPU baseline
+(`cpu_baseline`); without it those three keys are null.
 
 Multi-GPU: one process per GPU (torch.distributed.run).  Default = SURVEY.md 8(d)/8(e): the config's
 num_envs is the GLOBAL env count, split over the ranks (rank r owns envs [r N/R, (r+1) N/R) with its
@@ -99,9 +107,17 @@ def parse():
     p.add_argument("--cudnn-benchmark", type=int, default=None, choices=[0, 1],
                    help="MIOpen find mode (torch.backends.cudnn.benchmark) for the convolutions; default on for "
                         "pong; microrts runs immediate mode over the shipped find database (same solver picks)")
-    p.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--roofline-reps", type=int, default=200)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the measurements that take runs of their own: the GAE "
+                        "kernel's rooflines and (cartpole, one process) the CPU baseline; off by default")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed (rank 0) as DIR/<name>.npy: the "
+                        "updated parameters, the per-optimizer-step stats rows and gradient norms, the update's "
+                        "aggregated train stats, and the rollout's actions, log-probabilities, values, advantages "
+                        "and returns; float32 / float64, a fixed seeded sample of any array above 2^20 elements")
+    p.add_argument("--cpu-baseline-seconds", type=float, default=15.0, help="with --full")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    p.add_argument("--roofline-reps", type=int, default=200, help="with --full: launches of the GAE roofline")
     p.add_argument("--num-envs", type=int, default=None, help="override (rehearsal/debug only; not a bench line)")
     p.add_argument("--dp-rehearsal", action="store_true",
                    help="single process: run the data-parallel update path over a 1-rank RCCL group "
@@ -220,6 +236,116 @@ def cpu_baseline(args, N: int, T: int, algo_kw: dict) -> dict:
                                     "total_steps": est_small["minibatches_total"], "rel_error": round(err, 4)}}
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per dumped array; nine arrays of 4 B elements stay under 64 MB
+
+
+def dump_array(x):
+    """Flat host copy of one output (a tensor or an array) as float32 (float64 stays float64).  Above
+    DUMP_MAX_ELEMS elements: the elements at DUMP_MAX_ELEMS sorted indices drawn from a generator seeded
+    with 0, so every run and every build of the library samples the same positions."""
+    import numpy as np
+    import torch
+
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    dtype = np.float64 if x.dtype == torch.float64 else np.float32
+    x = x.detach().reshape(-1)
+    if x.numel() > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).integers(0, x.numel(), DUMP_MAX_ELEMS))
+        x = x[torch.from_numpy(idx).to(x.device)]
+    return x.cpu().numpy().astype(dtype, copy=False)
+
+
+def dump_outputs(out_dir: str, algo, update_out) -> None:
+    """--dump-outputs: what a caller of the timed path (PPO.learn_epoch) holds after the last timed step.
+    `update_out` is that step's PPO.update result (stats rows, gradient norms, value columns)."""
+    import dataclasses
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    stats, norms, _ = update_out
+    r = algo.last_update_rollout
+    ts = []
+    for name, v in dataclasses.asdict(algo.last_train_stats).items():
+        if not isinstance(v, dict):  # additional_losses: empty for PPO
+            ts.extend(np.asarray(v, np.float64).reshape(-1).tolist())
+    arrays = {"params": algo.flat.flat, "step_stats": stats, "grad_norms": norms,
+              "train_stats": np.asarray(ts, np.float64), "actions": r.actions, "logprobs": r.logprobs,
+              "values": r.values, "advantages": r.advantages, "returns": r.returns}
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), dump_array(x))
+
+
+def gae_rooflines(args, gen, algo, T: int, N: int, dev, traffic, traffic_source):
+    """--full: rooflines of the GAE kernel (named by the BASELINE metric) from launches of their own, at
+    the workload's shape and in the kernel's bandwidth regime.  Returns (roofline_gae,
+    roofline_gae_bandwidth_regime)."""
+    import torch
+
+    from rl_algo_impls_amd.gae import compute_advantages_device
+
+    # the launches are bracketed by a HIP event pair on the stream they are launched on (torch's current
+    # stream = the stream passed to rai_gae), so host launch overhead is not counted as kernel time
+    r = gen.rollout(gamma=algo.gamma, gae_lambda=algo.gae_lambda)
+    K = int(r.values.shape[2]) if r.values.dim() > 2 else 1
+    gae_bytes = (4 * T * N * K) * 4 + T * N + 4 * N * K + N  # r, V, adv, returns + starts + next V/starts
+    adv = torch.empty_like(r.values)
+    ret = torch.empty_like(r.values)
+
+    def gae():
+        compute_advantages_device(r.rewards, r.values, r.episode_starts, r.next_episode_starts, r.next_values,
+                                  algo.gamma, algo.gae_lambda, advantages_out=adv, returns_out=ret)
+
+    for _ in range(10):
+        gae()
+    torch.cuda.synchronize()
+    # park the stream behind a ~20 ms spin so every (event, launch, event) triple below is queued
+    # before the GPU reaches it: the pairs then time the kernel, not the Python launch gap
+    torch.cuda._sleep(50_000_000)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.roofline_reps):  # back to back: kernel time + the kernel-boundary gap
+        gae()
+    e1.record()
+    torch.cuda.synchronize()
+    gae_us = e0.elapsed_time(e1) * 1e3 / args.roofline_reps
+    # the same kernel in its bandwidth regime (SURVEY.md 8(d)'s (128, 2^20) microbench shape): the
+    # workload shape above is bound by the serial fp64 chain and launch latency, not by HBM
+    Tl, Nl = 128, 1 << 20
+    gl_ = torch.Generator(device=dev).manual_seed(3)
+    rl_, vl_ = (torch.randn((Tl, Nl), device=dev, generator=gl_) for _ in range(2))
+    esl = (torch.rand((Tl, Nl), device=dev, generator=gl_) < 0.01).to(torch.uint8)
+    nesl = torch.zeros(Nl, dtype=torch.uint8, device=dev)
+    nvl, advl, retl = torch.randn(Nl, device=dev, generator=gl_), torch.empty_like(rl_), torch.empty_like(rl_)
+    large = lambda: compute_advantages_device(rl_, vl_, esl, nesl, nvl, 0.99, 0.95, advantages_out=advl,
+                                              returns_out=retl)
+    for _ in range(3):
+        large()
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(20):
+        large()
+    e1.record()
+    torch.cuda.synchronize()
+    large_us = e0.elapsed_time(e1) * 1e3 / 20
+    large_bytes = 16 * Tl * Nl + Tl * Nl + 5 * Nl
+    # rai_gae's pick at >= 2^18 columns, K = 1 (csrc/gae.hip): the streaming kernel, 1024 threads,
+    # nontemporal loads / stores
+    roof_gae_large = {"kernel": "gae_stream_kernel<double, 4, true, 1024, true>", "shape": [Tl, Nl, 1], "bound": "hbm",
+                      "achieved": round(large_bytes / (large_us * 1e-6) / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
+                      "frac": round(large_bytes / (large_us * 1e-6) / 1e9 / 8000.0, 4), "avg_us": round(large_us, 2),
+                      "bytes_per_launch": large_bytes}
+    # the instantiation rai_gae picks (csrc/gae.hip): columns per workgroup by column count
+    C = N * K
+    gae_name = "gae_kernel<double, %d>" % (64 if C >= 256 * 64 else (32 if C >= 256 * 32 else 16))
+    roof_gae = {"kernel": gae_name, "bound": "hbm", "achieved": round(gae_bytes / (gae_us * 1e-6) / 1e9, 1),
+                "peak": 8000.0, "unit": "GB/s", "frac": round(gae_bytes / (gae_us * 1e-6) / 1e9 / 8000.0, 4),
+                "traffic": traffic(gae_name), "traffic_source": traffic_source(gae_name), "avg_us": round(gae_us, 3),
+                "bytes_per_launch": gae_bytes}
+    return roof_gae, roof_gae_large
+
+
 def _diagnostics(tag: str) -> None:
     """RAI_DIAG_DIR=<dir>: Python stacks of every thread on a fatal signal (faulthandler) and
     this process's /proc/self/maps at each stage, so a native crash's PCs (which are per process
@@ -309,7 +435,6 @@ def main():
     _pkgload.load()
     from rl_algo_impls_amd import _lib
     from rl_algo_impls_amd.envs import SyntheticVecEnv
-    from rl_algo_impls_amd.gae import compute_advantages_device
     from rl_algo_impls_amd.policy import ActorCritic
     from rl_algo_impls_amd.ppo import PPO
     from rl_algo_impls_amd.rollout import SyncStepRolloutGenerator
@@ -418,6 +543,15 @@ def main():
              and algo.batch_size > _lib.RAI_MLP_EPOCH_MAX_B)
     nmb = (T * N + algo.batch_size - 1) // algo.batch_size
     large_steps = large
+    last_update = {}  # --dump-outputs: the latest PPO.update result (stats rows, grad norms, value columns)
+    if args.dump_outputs:
+        update = algo.update
+
+        def keep_update(r):
+            last_update["out"] = update(r)
+            return last_update["out"]
+
+        algo.update = keep_update
     _diagnostics("setup")
     for i in range(args.warmup):
         tw = time.perf_counter()
@@ -453,59 +587,9 @@ def main():
     total_steps = args.steps * T * N * world
     value = total_steps / elapsed
 
-    # ---- roofline of the GAE kernel (named by the BASELINE metric): each launch bracketed by its
-    # own HIP event pair on the stream it is launched on (torch's current stream = the stream passed
-    # to rai_gae), so host launch overhead between launches is not counted as kernel time
-    r = gen.rollout(gamma=algo.gamma, gae_lambda=algo.gae_lambda)
-    K = int(r.values.shape[2]) if r.values.dim() > 2 else 1
-    gae_bytes = (4 * T * N * K) * 4 + T * N + 4 * N * K + N  # r, V, adv, returns + starts + next V/starts
-    adv = torch.empty_like(r.values)
-    ret = torch.empty_like(r.values)
+    if args.dump_outputs and rank == 0 and last_update:
+        dump_outputs(args.dump_outputs, algo, last_update["out"])
 
-    def gae():
-        compute_advantages_device(r.rewards, r.values, r.episode_starts, r.next_episode_starts, r.next_values,
-                                  algo.gamma, algo.gae_lambda, advantages_out=adv, returns_out=ret)
-
-    for _ in range(10):
-        gae()
-    torch.cuda.synchronize()
-    # park the stream behind a ~20 ms spin so every (event, launch, event) triple below is queued
-    # before the GPU reaches it: the pairs then time the kernel, not the Python launch gap
-    torch.cuda._sleep(50_000_000)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.roofline_reps):  # back to back: kernel time + the kernel-boundary gap
-        gae()
-    e1.record()
-    torch.cuda.synchronize()
-    gae_us = e0.elapsed_time(e1) * 1e3 / args.roofline_reps
-    # the same kernel in its bandwidth regime (SURVEY.md 8(d)'s (128, 2^20) microbench shape): the
-    # workload shape above is bound by the serial fp64 chain and launch latency, not by HBM
-    Tl, Nl = 128, 1 << 20
-    gl_ = torch.Generator(device=dev).manual_seed(3)
-    rl_, vl_ = (torch.randn((Tl, Nl), device=dev, generator=gl_) for _ in range(2))
-    esl = (torch.rand((Tl, Nl), device=dev, generator=gl_) < 0.01).to(torch.uint8)
-    nesl = torch.zeros(Nl, dtype=torch.uint8, device=dev)
-    nvl, advl, retl = torch.randn(Nl, device=dev, generator=gl_), torch.empty_like(rl_), torch.empty_like(rl_)
-    large = lambda: compute_advantages_device(rl_, vl_, esl, nesl, nvl, 0.99, 0.95, advantages_out=advl,
-                                              returns_out=retl)
-    for _ in range(3):
-        large()
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(20):
-        large()
-    e1.record()
-    torch.cuda.synchronize()
-    large_us = e0.elapsed_time(e1) * 1e3 / 20
-    large_bytes = 16 * Tl * Nl + Tl * Nl + 5 * Nl
-    # rai_gae's pick at >= 2^18 columns, K = 1 (csrc/gae.hip): the streaming kernel, 1024 threads,
-    # nontemporal loads / stores
-    roof_gae_large = {"kernel": "gae_stream_kernel<double, 4, true, 1024, true>", "shape": [Tl, Nl, 1], "bound": "hbm",
-                      "achieved": round(large_bytes / (large_us * 1e-6) / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
-                      "frac": round(large_bytes / (large_us * 1e-6) / 1e9 / 8000.0, 4), "avg_us": round(large_us, 2),
-                      "bytes_per_launch": large_bytes}
-    del rl_, vl_, esl, advl, retl
     workload = f"ppo {args.config} num_envs={N}/rank n_steps={T}"
     if args.batch_policy == "scaled":
         workload += f" batch_policy=scaled batch={algo.batch_size}"
@@ -532,13 +616,9 @@ def main():
             return f"{pmc_src}: measured on another librai_amd.so build (sha256 {str(e.get('lib_sha256'))[:12]}), not reported"
         return f"{pmc_src} (2 x FETCH_SIZE + WRITE_SIZE per launch, same library sha256 {lib_sha[:12]})"
 
-    # the instantiation rai_gae picks (csrc/gae.hip): columns per workgroup by column count
-    C = N * K
-    gae_name = "gae_kernel<double, %d>" % (64 if C >= 256 * 64 else (32 if C >= 256 * 32 else 16))
-    roof_gae = {"kernel": gae_name, "bound": "hbm", "achieved": round(gae_bytes / (gae_us * 1e-6) / 1e9, 1),
-                "peak": 8000.0, "unit": "GB/s", "frac": round(gae_bytes / (gae_us * 1e-6) / 1e9 / 8000.0, 4),
-                "traffic": traffic(gae_name), "traffic_source": traffic_source(gae_name), "avg_us": round(gae_us, 3),
-                "bytes_per_launch": gae_bytes}
+    roof_gae = roof_gae_large = None
+    if args.full:
+        roof_gae, roof_gae_large = gae_rooflines(args, gen, algo, T, N, dev, traffic, traffic_source)
     # rows one update's epoch launches cover: the whole env group's under the replicated data-parallel update
     # (every rank runs the single-process update over the gathered rollout), this rank's otherwise
     TN = T * N * (world if getattr(algo, "dp_update_mode", "exchange") == "replicated" and world > 1 else 1)
@@ -631,7 +711,7 @@ def main():
         roof_lat = None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "cartpole":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "cartpole":
         cpu = cpu_baseline(args, N, T, dict(algo_kw, batch_size=algo.batch_size))
 
     if rank == 0:
@@ -642,6 +722,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong" if split else "weak",
