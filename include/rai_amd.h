@@ -282,6 +282,52 @@ int rai_conv2d_wgrad_v(const float* x, const float* dz, int64_t B, int32_t H, in
                        int64_t workspace_bytes, int32_t target_wgs, int32_t pf, void* stream);
 
 /* --------------------------------------------------------------------------
+ * IMPALA CNN encoder (cnn_style: impala; rl_algo_impls/shared/encoder/impala_cnn.py:11-92), csrc/conv3x3.hip.
+ * Every convolution is 3x3, stride 1, zero padding 1 (handled in-kernel: no padded copy).  Activations NHWC
+ * fp32 (B, H, W, C), weights channels_last (Co, 3, 3, Ci), f32 MFMA, deterministic (fixed summation order,
+ * no atomics).  Ci % 16 == 0 and Co % 16 == 0, both in [16, 128], float pointers 16-B aligned:
+ * RAI_E_UNSUPPORTED otherwise (nothing is launched).
+ *
+ * rai_conv3x3_fwd: y = post(conv(pre(x), w) + b + res).  pre_relu: ReLU applied to x as it is loaded (the
+ * pre-activation of a residual block; x itself stays raw for the skip).  res: NULL, or a tensor of y's
+ * NHWC shape added in the store.  post_relu: ReLU in the store.  out_nchw != 0: y in nn.Flatten's
+ * (B, Co * H * W) order.
+ * rai_conv3x3_fwd_first: the first layer, Ci 3 or 4; x uint8 NHWC (x_is_u8 != 0: read as x / x_divisor,
+ * IEEE division, the value cnn.py:24-27's obs.float() / range_size gives) or fp32 NHWC (4-B aligned);
+ * y = conv(x, w) + b, NHWC.
+ * rai_conv3x3_dgrad: dx = mask(conv(dz, rot180(w)^T)) + res: the input gradient (dz (B, H, W, Co),
+ * dx (B, H, W, Ci)), zeroed where the saved tensor m (dx's shape, or NULL) is <= 0 (threshold_backward),
+ * then res (dx's shape, or NULL) added.  The forward's device code with a transposed weight index.
+ * ------------------------------------------------------------------------ */
+int rai_conv3x3_fwd(const float* x, const float* w, const float* b, const float* res, int64_t B, int32_t H, int32_t W,
+                    int32_t Ci, int32_t Co, int32_t pre_relu, int32_t post_relu, int32_t out_nchw, float* y,
+                    void* stream);
+int rai_conv3x3_fwd_first(const void* x, int32_t x_is_u8, float x_divisor, const float* w, const float* b, int64_t B,
+                          int32_t H, int32_t W, int32_t Ci, int32_t Co, float* y, void* stream);
+int rai_conv3x3_dgrad(const float* dz, const float* w, const float* m, const float* res, int64_t B, int32_t H,
+                      int32_t W, int32_t Ci, int32_t Co, float* dx, void* stream);
+/* dw[co][kh][kw][ci] = sum_p dz[p][co] * pre(x)[p + (kh - 1, kw - 1)][ci] and db[co] = sum_p dz[p][co]
+ * (db may be NULL), stored (accumulate == 0) or added (the flat .grad views).  Two launches: per-wave
+ * partial tiles in workspace (rai_conv3x3_wgrad_workspace_bytes, 16-B aligned, no zeroing needed), then a
+ * fixed-order sum.  rai_conv3x3_wgrad_first: the first layer (Ci 3 or 4, x as rai_conv3x3_fwd_first). */
+int64_t rai_conv3x3_wgrad_workspace_bytes(int64_t B, int32_t H, int32_t W, int32_t Ci, int32_t Co);
+int rai_conv3x3_wgrad(const float* x, const float* dz, int64_t B, int32_t H, int32_t W, int32_t Ci, int32_t Co,
+                      int32_t pre_relu, float* dw, float* db, int32_t accumulate, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+int rai_conv3x3_wgrad_first(const void* x, int32_t x_is_u8, float x_divisor, const float* dz, int64_t B, int32_t H,
+                            int32_t W, int32_t Ci, int32_t Co, float* dw, float* db, int32_t accumulate,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+/* nn.MaxPool2d(3, stride=2, padding=1) over NHWC fp32, C % 4 == 0: y (B, OH, OW, C) with
+ * OH = (H - 1) / 2 + 1, OW likewise; padding counts as -inf.  argmax (uint8, y's shape, 4-B aligned): the
+ * window position kh * 3 + kw of the maximum, the first in-bounds position among equals; a NaN in the
+ * window propagates (as torch).  Backward, gather form: every dx (B, H, W, C) element is written as the
+ * sum, in (oh, ow) order, of dy over the windows whose argmax names it. */
+int rai_maxpool3x3s2_fwd(const float* x, int64_t B, int32_t H, int32_t W, int32_t C, float* y, uint8_t* argmax,
+                         void* stream);
+int rai_maxpool3x3s2_bwd(const float* dy, const uint8_t* argmax, int64_t B, int32_t H, int32_t W, int32_t C,
+                         float* dx, void* stream);
+
+/* --------------------------------------------------------------------------
  * Device-resident hyperparameters and training state.
  * These live in HBM so a captured hipGraph replays against values the host
  * rewrites once per update (schedules: rl_algo_impls/shared/callbacks/

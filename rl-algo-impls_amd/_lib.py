@@ -212,6 +212,15 @@ _SIGNATURES = {
     "rai_conv2d_dgrad": (C.c_int, [_vp, _vp, _i64] + [_i32] * 7 + [_vp, _vp]),
     "rai_conv2d_dgrad_v": (C.c_int, [_vp, _vp, _i64] + [_i32] * 7 + [_vp, _i32, _vp]),
     "rai_conv2d_dgrad_relu": (C.c_int, [_vp, _vp, _vp, _i64] + [_i32] * 7 + [_vp, _vp]),
+    "rai_conv3x3_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64] + [_i32] * 7 + [_vp, _vp]),
+    "rai_conv3x3_fwd_first": (C.c_int, [_vp, _i32, C.c_float, _vp, _vp, _i64] + [_i32] * 4 + [_vp, _vp]),
+    "rai_conv3x3_dgrad": (C.c_int, [_vp, _vp, _vp, _vp, _i64] + [_i32] * 4 + [_vp, _vp]),
+    "rai_conv3x3_wgrad_workspace_bytes": (_i64, [_i64] + [_i32] * 4),
+    "rai_conv3x3_wgrad": (C.c_int, [_vp, _vp, _i64] + [_i32] * 5 + [_vp, _vp, _i32, _vp, _i64, _vp]),
+    "rai_conv3x3_wgrad_first": (C.c_int, [_vp, _i32, C.c_float, _vp, _i64] + [_i32] * 4 + [_vp, _vp, _i32, _vp, _i64,
+                                                                                         _vp]),
+    "rai_maxpool3x3s2_fwd": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "rai_maxpool3x3s2_bwd": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rai_bias_relu_bwd_nchw": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     "rai_mlp_ppo_workspace_bytes": (_i64, [C.c_int64, C.c_int32]),
     "rai_mlp_ppo_grads": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32,

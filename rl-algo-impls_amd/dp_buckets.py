@@ -109,8 +109,9 @@ class GradBuckets:
 
 
 def nature_cnn_buckets(policy, flat) -> Optional[tuple]:
-    """(bounds, triggers) for a NatureCNN ActorCritic: bucket 0 = the convolutions, bucket 1 = fc +
-    heads triggered by the fc weight's gradient.  None for other policies (one bucket)."""
+    """(bounds, triggers) for a CNN-encoder ActorCritic (NatureCNN, or the IMPALA CNN: both keep the
+    Linear at fc[1]): bucket 0 = the convolutions, bucket 1 = fc + heads triggered by the fc weight's
+    gradient.  None for other policies (one bucket)."""
     try:
         enc = policy.network._feature_extractor.feature_extractor
         fc_w = enc.fc[1].weight

@@ -7,7 +7,8 @@ rl_algo_impls/shared/policy/actor_critic_network/connected_trio.py:17-116):
   network._feature_extractor   Encoder: Flatten for 1-D Box obs
                                (shared/encoder/encoder.py:51-58) or NatureCnn for
                                3-D Box obs (shared/encoder/nature_cnn.py:10-53,
-                               shared/encoder/cnn.py:24-72; /range_size prescale)
+                               shared/encoder/cnn.py:24-72; /range_size prescale), or
+                               ImpalaCnn with cnn_style="impala" (shared/encoder/impala_cnn.py)
   network._pi                  CategoricalActorHead._fc (shared/actor/categorical.py:57-87)
                                or GaussianActorHead.{log_std, mu_net} (shared/actor/gaussian.py:19-61)
   network._v                   CriticHead._fc = Sequential(mlp) (shared/policy/critic.py:11-41)
@@ -126,6 +127,9 @@ class NatureCnnEncoder(nn.Module):
         # the divisor as a device scalar (non-persistent: not in the state_dict), see forward()
         self.register_buffer("_range", torch.tensor(self.range_size, dtype=torch.float32), persistent=False)
 
+    def conv_weights(self) -> list:
+        return [self.cnn[i].weight for i in (0, 2, 4)]
+
     def _u8_input(self, obs: torch.Tensor) -> bool:
         """conv1 reads the uint8 frames itself (cnn_ops RAI_CONV_U8): 4 channels, the fused ReLU path."""
         from . import cnn_ops
@@ -204,17 +208,162 @@ class NatureCnnEncoder(nn.Module):
         return self._trunk_fused(x.contiguous(memory_format=torch.channels_last))
 
 
+class ResidualBlock(nn.Module):  # shared/encoder/impala_cnn.py:11-31
+    def __init__(self, channels: int, activation, init_layers_orthogonal: bool = False):
+        super().__init__()
+        self.residual = nn.Sequential(
+            activation(),
+            layer_init(nn.Conv2d(channels, channels, 3, padding=1), init_layers_orthogonal),
+            activation(),
+            layer_init(nn.Conv2d(channels, channels, 3, padding=1), init_layers_orthogonal),
+        )
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return x + self.residual(x)
+
+
+class ConvSequence(nn.Module):  # shared/encoder/impala_cnn.py:34-54
+    def __init__(self, in_channels: int, out_channels: int, activation, init_layers_orthogonal: bool = False):
+        super().__init__()
+        self.seq = nn.Sequential(
+            layer_init(nn.Conv2d(in_channels, out_channels, 3, padding=1), init_layers_orthogonal),
+            nn.MaxPool2d(3, stride=2, padding=1),
+            ResidualBlock(out_channels, activation, init_layers_orthogonal),
+            ResidualBlock(out_channels, activation, init_layers_orthogonal),
+        )
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.seq(x)
+
+
+class ImpalaCnnEncoder(nn.Module):
+    """shared/encoder/impala_cnn.py ImpalaCnn + cnn.py FlattenedCnnEncoder (keys cnn.{s}.seq.0,
+    cnn.{s}.seq.{2,3}.residual.{1,3}, fc.1).  On the GPU with ReLU activations the ConvSequences run on
+    the fused MFMA kernels of impala_ops.py (csrc/conv3x3.hip); elsewhere the modules themselves run
+    (F.conv2d / F.max_pool2d)."""
+
+    def __init__(self, obs_space, activation, cnn_init_layers_orthogonal: Optional[bool],
+                 linear_init_layers_orthogonal: bool, cnn_flatten_dim: int,
+                 impala_channels: Sequence[int] = (16, 32, 32)):
+        super().__init__()
+        if cnn_init_layers_orthogonal is None:
+            cnn_init_layers_orthogonal = False
+        self.range_size = float(np.max(obs_space.high) - np.min(obs_space.low))
+        in_channels = obs_space.shape[0]
+        sequences = []
+        for out_channels in impala_channels:
+            sequences.append(ConvSequence(in_channels, int(out_channels), activation, cnn_init_layers_orthogonal))
+            in_channels = int(out_channels)
+        sequences.append(activation())
+        self.cnn = nn.Sequential(*sequences)
+        with torch.no_grad():
+            dummy = torch.zeros((1,) + tuple(obs_space.shape))
+            n_flat = torch.flatten(self.cnn(dummy), start_dim=1).shape[1]
+        self.fc = nn.Sequential(
+            nn.Flatten(),
+            layer_init(nn.Linear(n_flat, cnn_flatten_dim), linear_init_layers_orthogonal),
+            activation(),
+        )
+        self.out_dim = cnn_flatten_dim
+        self._relu = activation is nn.ReLU
+        self.register_buffer("_range", torch.tensor(self.range_size, dtype=torch.float32), persistent=False)
+
+    def conv_weights(self) -> list:
+        from .impala_ops import convs
+
+        return [c.weight for c in convs(self)]
+
+    def _fusable(self, x: torch.Tensor) -> bool:
+        from .impala_ops import fusable
+
+        return _CHANNELS_LAST and _FUSED_EPILOGUES and fusable(self, x)
+
+    def _u8_input(self, obs: torch.Tensor) -> bool:
+        """The first convolution reads the uint8 frames itself (x / range_size in-kernel)."""
+        from . import cnn_ops
+
+        return cnn_ops._CONV_U8 and obs.dtype == torch.uint8 and self._fusable(obs)
+
+    def obs_transform(self, obs: torch.Tensor):
+        """As NatureCnnEncoder.obs_transform: uint8 channels_last frames where the first convolution
+        reads them (4 channels: the gather's uint8 transform takes no other count), else
+        obs.float() / range_size in channels_last; None outside the fused path."""
+        from . import _lib
+
+        C, H, W = (int(d) for d in obs.shape[-3:])
+        x = obs if obs.dim() == 4 else obs.reshape((-1, C, H, W))
+        if not (obs.dtype == torch.uint8 and C <= 4 and (H * W) % 4 == 0 and self._fusable(x)):
+            return None
+        kind = (_lib.RAI_XFORM_U8_CHW_TO_U8_HWC if C == 4 and self._u8_input(x)
+                else _lib.RAI_XFORM_U8_CHW_TO_F32_HWC)
+        return _lib.GatherXform(kind=kind, channels=C, hw=H * W, divisor=self.range_size)
+
+    def _input(self, obs: torch.Tensor, prepared: bool) -> torch.Tensor:
+        if prepared or self._u8_input(obs):
+            return obs
+        if obs.is_cuda:  # IEEE division by a device scalar (see NatureCnnEncoder.forward)
+            return obs.float() / self._range
+        return obs.float() / self.range_size
+
+    def forward(self, obs: torch.Tensor, prepared: bool = False) -> torch.Tensor:
+        if obs.dim() == 3:
+            obs = obs.unsqueeze(0)
+        x = self._input(obs, prepared)
+        if self._fusable(x):
+            return self.fc_relu(self._trunk_fused(x.contiguous(memory_format=torch.channels_last)))
+        if x.dtype == torch.uint8:
+            raise RuntimeError("ImpalaCnnEncoder: prepared uint8 frames outside the fused path")
+        if _CHANNELS_LAST and x.is_cuda:
+            x = x.contiguous(memory_format=torch.channels_last)
+        return self.fc(self.cnn(x))
+
+    def _trunk_fused(self, x: torch.Tensor) -> torch.Tensor:
+        """The ConvSequences and the final ReLU; the last residual block's store writes the flattened
+        (NCHW-order) fc input itself."""
+        from .impala_ops import conv_pool, res_block
+
+        n = len(self.cnn) - 1
+        for s in range(n):
+            seq = self.cnn[s].seq
+            x = conv_pool(seq[0], x, x_div=self.range_size if x.dtype == torch.uint8 else None)
+            x = res_block(seq[2], x)
+            x = res_block(seq[3], x, final=s == n - 1)
+        return x
+
+    def fc_relu(self, flat: torch.Tensor) -> torch.Tensor:
+        from .cnn_ops import linear_relu
+
+        return linear_relu(self.fc[1], flat)
+
+    def forward_trunk(self, obs: torch.Tensor, prepared: bool = False):
+        """The flattened, activated output of the last ConvSequence (the fc layer's input) where the
+        fused GPU path applies, else None (the caller then runs forward())."""
+        if obs.dim() == 3:
+            obs = obs.unsqueeze(0)
+        if not obs.is_cuda:
+            return None
+        x = self._input(obs, prepared)
+        if not self._fusable(x):
+            return None
+        return self._trunk_fused(x.contiguous(memory_format=torch.channels_last))
+
+
 class Encoder(nn.Module):  # shared/encoder/encoder.py:25-73
     def __init__(self, obs_space, activation, init_layers_orthogonal: bool = False,
                  cnn_flatten_dim: int = 512, cnn_style: str = "nature",
-                 cnn_layers_init_orthogonal: Optional[bool] = None):
+                 cnn_layers_init_orthogonal: Optional[bool] = None,
+                 impala_channels: Sequence[int] = (16, 32, 32)):
         super().__init__()
         if is_box(obs_space) and len(obs_space.shape) == 3:
-            if cnn_style != "nature":
-                raise NotImplementedError(f"cnn_style={cnn_style} is outside the hot-path scope")
             self.kind = "cnn"
-            self.feature_extractor = NatureCnnEncoder(obs_space, activation, cnn_layers_init_orthogonal,
-                                                      init_layers_orthogonal, cnn_flatten_dim)
+            if cnn_style == "nature":
+                self.feature_extractor = NatureCnnEncoder(obs_space, activation, cnn_layers_init_orthogonal,
+                                                          init_layers_orthogonal, cnn_flatten_dim)
+            elif cnn_style == "impala":
+                self.feature_extractor = ImpalaCnnEncoder(obs_space, activation, cnn_layers_init_orthogonal,
+                                                          init_layers_orthogonal, cnn_flatten_dim, impala_channels)
+            else:
+                raise NotImplementedError(f"cnn_style={cnn_style} is outside the hot-path scope")
             self.out_dim = self.feature_extractor.out_dim
         elif is_box(obs_space) and len(obs_space.shape) == 1:
             self.kind = "flat"
@@ -328,14 +477,15 @@ class CriticHead(nn.Module):
 class ConnectedTrioNetwork(nn.Module):
     def __init__(self, observation_space, action_space, pi_hidden_sizes=None, v_hidden_sizes=None,
                  init_layers_orthogonal=True, activation_fn="tanh", log_std_init=-0.5,
-                 cnn_flatten_dim=512, cnn_style="nature", cnn_layers_init_orthogonal=None):
+                 cnn_flatten_dim=512, cnn_style="nature", cnn_layers_init_orthogonal=None,
+                 impala_channels=(16, 32, 32)):
         super().__init__()
         pi_hidden_sizes = pi_hidden_sizes if pi_hidden_sizes is not None else default_hidden_sizes(observation_space)
         v_hidden_sizes = v_hidden_sizes if v_hidden_sizes is not None else default_hidden_sizes(observation_space)
         activation = ACTIVATION[activation_fn]
         self.activation_fn = activation_fn
         self._feature_extractor = Encoder(observation_space, activation, init_layers_orthogonal,
-                                          cnn_flatten_dim, cnn_style, cnn_layers_init_orthogonal)
+                                          cnn_flatten_dim, cnn_style, cnn_layers_init_orthogonal, impala_channels)
         in_dim = self._feature_extractor.out_dim
         if is_discrete(action_space):
             self._pi = CategoricalActorHead(action_space.n, in_dim, tuple(pi_hidden_sizes), activation,
@@ -392,7 +542,8 @@ class ActorCritic(nn.Module):
                  strides_per_level=None, deconv_strides_per_level=None, encoder_residual_blocks_per_level=None,
                  decoder_residual_blocks_per_level=None, increment_kernel_size_on_down_conv=False,
                  output_activation_fn="identity", subaction_mask=None, critic_shares_backbone=None,
-                 save_critic_separate=None, shared_critic_head=None, normalization=None, **kwargs):
+                 save_critic_separate=None, shared_critic_head=None, normalization=None,
+                 impala_channels=(16, 32, 32), **kwargs):
         super().__init__()
         if use_sde or squash_output:
             raise NotImplementedError("gSDE / squash_output are outside the hot-path scope")
@@ -429,7 +580,7 @@ class ActorCritic(nn.Module):
             self.network = ConnectedTrioNetwork(env.single_observation_space, env.single_action_space,
                                                 pi_hidden_sizes, v_hidden_sizes, init_layers_orthogonal,
                                                 activation_fn, log_std_init, cnn_flatten_dim, cnn_style,
-                                                cnn_layers_init_orthogonal)
+                                                cnn_layers_init_orthogonal, tuple(impala_channels))
         self._device: Optional[torch.device] = None
         # policy.py:31-36: the env's normalisation statistics travel with the checkpoint
         from .wrappers import NormalizeObservation, NormalizeReward, find_wrapper
@@ -471,12 +622,11 @@ class ActorCritic(nn.Module):
         return ACForward(*self.network(obs, action, action_masks))
 
     def channels_last_params(self) -> list:
-        """Parameters the flat buffer should store channels_last (optim.FlatParams): the NatureCNN
+        """Parameters the flat buffer should store channels_last (optim.FlatParams): the CNN encoder's
         convolution weights when the activations are NHWC on the GPU."""
         if self.gridnet or self.network._feature_extractor.kind != "cnn" or not _CHANNELS_LAST:
             return []
-        cnn = self.network._feature_extractor.feature_extractor.cnn
-        return [cnn[i].weight for i in (0, 2, 4)]
+        return self.network._feature_extractor.feature_extractor.conv_weights()
 
     def obs_transform(self, obs: torch.Tensor):
         """The gather transform (rai_gather_xform) that prepares rollout obs rows for forward(...,
