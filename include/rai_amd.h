@@ -803,6 +803,112 @@ int rai_mlp_ppo_epoch_xdp(float* params, float* exp_avg, float* exp_avg_sq, cons
                           int32_t max_stats, float* norms, int32_t max_norms, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* --------------------------------------------------------------------------
+ * DQN (algo `dqn`): device replay ring, sampler, TD loss, fused output head,
+ * greedy action and target-network update (csrc/dqn.hip).
+ *
+ * Replay ring.  Replaces the `deque(maxlen=buffer_size)` of per-transition tuples of
+ * rl_algo_impls/rollout/replay_buffer_rollout_generator.py:46,63-68.  Five fields in HBM:
+ * obs / next_obs (capacity, row_bytes) raw bytes in the env's dtype (uint8 frames or float32
+ * vectors; no widening), actions int64, rewards f32, dones u8.  `state` is a device-resident
+ * block that the kernels below read AND update, so a captured graph needs no host-side
+ * argument patching: head = the slot the next push writes, len = live transitions (saturates
+ * at capacity), draws = sampler calls so far.  arrivals is the kernels' block-arrival counter
+ * (0 between launches); err is a sticky device-side flag (1: a sample asked for more rows than
+ * len, 2: an injected index outside [0, len)); a launch that sets it copies no row for the
+ * offending request.  The caller zeroes the block once.  rai_replay_ring itself is a host
+ * struct read at call time (its pointers are then fixed in a captured launch).
+ *
+ * rai_replay_push appends N transitions (device staging buffers, row i of every field) in one
+ * launch: slot (head + i) % capacity, wrapping around the end and overwriting the oldest, which
+ * is deque(maxlen) order; then head and len advance on the device.  N > capacity: RAI_E_SHAPE.
+ *
+ * rai_replay_sample replaces `random.sample(self.buffer, batch_size)` and the per-field
+ * torch.as_tensor(list) rebuild of replay_buffer_rollout_generator.py:72-84 in one launch.
+ * inject == NULL: row i is deque position p_key(i), the first B outputs of the keyed Feistel
+ * bijection of rai_feistel_permutation over [0, len) with key = seed + 0x9E3779B97F4A7C15 *
+ * draws (mod 2^64): B distinct positions, uniform over the live transitions, no sort and no
+ * rejection loop; draws is then incremented on the device.  inject != NULL (device, B int64):
+ * caller-supplied deque positions (0 = oldest), e.g. the reference's own draws; draws is left
+ * alone.  slots_out (B int64, may be NULL) receives the ring slots
+ * (head - len + position) mod capacity.  The five *_out batch buffers receive the gathered
+ * rows (same launch); pass all five NULL for the indices only (then rai_gather_rows over
+ * slots_out gives the same rows).  B > capacity: RAI_E_SHAPE on the host; B > len: err = 1.
+ * Row sizes: any; copied 16, 4 or 1 bytes at a time by size and alignment.
+ * ------------------------------------------------------------------------ */
+typedef struct rai_replay_state {
+  int64_t head;
+  int64_t len;
+  int64_t draws;
+  int32_t arrivals;
+  int32_t err;
+} rai_replay_state;
+typedef struct rai_replay_ring {
+  void* obs;
+  void* next_obs;
+  int64_t* actions;
+  float* rewards;
+  uint8_t* dones;
+  int64_t capacity;
+  int64_t row_bytes;
+  rai_replay_state* state;
+} rai_replay_ring;
+int rai_replay_push(const rai_replay_ring* ring, const void* obs, const void* next_obs, const int64_t* actions,
+                    const float* rewards, const uint8_t* dones, int64_t N, void* stream);
+int rai_replay_sample(const rai_replay_ring* ring, uint64_t seed, int64_t B, const int64_t* inject,
+                      int64_t* slots_out, void* obs_out, void* next_obs_out, int64_t* actions_out,
+                      float* rewards_out, uint8_t* dones_out, void* stream);
+
+/* TD target, smooth-L1 loss and its gradient in one launch.  Replaces rl_algo_impls/dqn/dqn.py:114-117
+ * (target = r + ~d * gamma * target_q(next_o).max(1).values; gather; F.smooth_l1_loss) and the loss's
+ * autograd backward down to q.  q, q_next_target (B, A) f32; actions int64; rewards f32; dones u8.
+ *   target_out[b] = r_b + (((float)!d_b * gamma) * max_a q_next[b, a])   torch's own f32 operation
+ *     order: separately rounded multiplies and add (no FMA), a multiply by 0 rather than a select, so a
+ *     done row with an infinite q_next is NaN as in torch; the row max propagates NaN as torch.max does.
+ *   loss_out[0]   = mean_b smooth_l1(q[b, a_b] - target_b), beta = 1 (rows summed in a fixed order in
+ *     double; torch sums in f32, so only the summation order differs)
+ *   dq_out (B, A) = 0 except clamp(q[b, a_b] - target_b, -1, 1) / B at (b, a_b), the division as torch
+ *     performs it on the device and in smooth_l1's backward: a multiply by the f32 reciprocal of B.
+ * A <= 256 (RAI_E_UNSUPPORTED beyond).  An action outside [0, A) makes its row's loss and gradient NaN. */
+#define RAI_DQN_MAX_A 256
+int rai_dqn_td_loss(const float* q, const float* q_next_target, const int64_t* actions, const float* rewards,
+                    const uint8_t* dones, int64_t B, int32_t A, float gamma, float* target_out, float* loss_out,
+                    float* dq_out, void* stream);
+
+/* The final Linear(H -> A) of the online and the target Q network fused with the TD loss (dqn.py:114-117
+ * over rl_algo_impls/dqn/q_net.py:34-41's last layer).  h / h_next (B, H): the two networks' last hidden
+ * activations; w (A, H), b (A) online; wt, bt target.
+ * Forward (one launch per row block plus a fixed-order loss reduction): q_next = h_next wt^T + bt, its row
+ * max, q[b, a_b] = h_b . w[a_b] + b[a_b], target and loss as rai_dqn_td_loss; g_out[b] = clamp(q[b, a_b] -
+ * target_b, -1, 1) / B (dq's one non-zero per row).  q_out / q_next_out (B, A) are optional (NULL in the
+ * trainer; tests feed them to rai_dqn_td_loss).
+ * Backward (one launch), from g: dh[b, :] = g_b * w[a_b, :];  dw[a, :] = sum_{b: a_b = a} g_b * h_b in
+ * ascending b;  db[a] = sum g_b: no dense GEMM and no (B, A) gradient tensor.  dw / db are written
+ * (accumulate == 0) or added to (accumulate != 0: the flat .grad views, as the heads above).
+ * Supported: 1 <= H <= 512, 1 <= A <= 32, f32 (else RAI_E_UNSUPPORTED: the caller takes torch's linear +
+ * rai_dqn_td_loss).  workspace >= rai_dqn_head_workspace_bytes(B). */
+#define RAI_DQN_HEAD_MAX_H 512
+#define RAI_DQN_HEAD_MAX_A 32
+int64_t rai_dqn_head_workspace_bytes(int64_t B);
+int rai_dqn_head_fwd(const float* h, const float* h_next, const float* w, const float* b, const float* wt,
+                     const float* bt, const int64_t* actions, const float* rewards, const uint8_t* dones,
+                     int64_t B, int32_t H, int32_t A, float gamma, float* target_out, float* loss_out,
+                     float* g_out, float* q_out, float* q_next_out, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int rai_dqn_head_bwd(const float* h, const float* w, const int64_t* actions, const float* g, int64_t B, int32_t H,
+                     int32_t A, float* dh, float* dw, float* db, int32_t accumulate, void* stream);
+
+/* Greedy action of DQNPolicy.act (rl_algo_impls/dqn/policy.py:56, q.argmax(axis=1)): out[b] (int64) = the
+ * first index of row b's maximum; a NaN counts as the maximum, as in torch.  x (B, A) f32, A >= 1. */
+int rai_argmax_rows(const float* x, int64_t B, int32_t A, int64_t* out, void* stream);
+
+/* Target-network update over the whole flat parameter buffer in one launch.  Replaces the per-parameter loop
+ * of dqn.py:125-131: target = tau * p + (1 - tau) * target with the reference's rounding: tau and
+ * one_minus_tau (formed as the double 1 - tau by the caller) are cast to f32, two multiplies and an add,
+ * unfused.  tau == 1 is an exact copy. */
+int rai_polyak_update(float* target, const float* params, int64_t n, double tau, double one_minus_tau,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

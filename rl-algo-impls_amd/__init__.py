@@ -16,11 +16,15 @@ _LAZY = {
     "compute_advantages_device": "gae",
     "PPO": "ppo",
     "A2C": "a2c",
+    "DQN": "dqn",
+    "DQNPolicy": "dqn",
+    "ReplayBufferRolloutGenerator": "replay",
     "ActorCritic": "policy",
     "SyncStepRolloutGenerator": "rollout",
     "DeviceRollout": "rollout",
     "Batch": "rollout",
     "ALGOS": "registry",
+    "ALL_ALGOS": "registry",
     "POLICIES": "registry",
     "DEFAULT_ROLLOUT_GENERATORS": "registry",
 }

@@ -24,6 +24,9 @@ RAI_MLP_EPOCH_MAX_B = 256  # rai_mlp_ppo_epoch's one-launch epoch kernels; large
 RAI_WIDE_MAX_H = 256
 RAI_WIDE_MAX_IN = 64
 RAI_WIDE_MAX_OUT = 8
+RAI_DQN_MAX_A = 256
+RAI_DQN_HEAD_MAX_H = 512
+RAI_DQN_HEAD_MAX_A = 32
 RAI_STAT_STRIDE = 5 + 2 * RAI_MAX_K
 ABI_VERSION = 1
 # the RAI_E_* return codes of include/rai_amd.h (tests/test_boundary.py checks them against the header)
@@ -111,6 +114,20 @@ class MlpWideDesc(C.Structure):
         ("activation", C.c_int32),
         ("accumulate", C.c_int32),
     ]
+
+
+class ReplayState(C.Structure):
+    """Mirror of rai_replay_state (the replay ring's device-resident block)."""
+
+    _fields_ = [("head", C.c_int64), ("len", C.c_int64), ("draws", C.c_int64), ("arrivals", C.c_int32),
+                ("err", C.c_int32)]
+
+
+class ReplayRing(C.Structure):
+    """Mirror of rai_replay_ring (host struct, read at call time)."""
+
+    _fields_ = [("obs", C.c_void_p), ("next_obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p),
+                ("dones", C.c_void_p), ("capacity", C.c_int64), ("row_bytes", C.c_int64), ("state", C.c_void_p)]
 
 
 class OptimHparams(C.Structure):
@@ -253,6 +270,14 @@ _SIGNATURES = {
     "rai_mlp_ppo_epoch_xdp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32,
                                         _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32,
                                         _vp, _i64, _vp]),
+    "rai_replay_push": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "rai_replay_sample": (C.c_int, [_vp, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rai_dqn_td_loss": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp]),
+    "rai_dqn_head_workspace_bytes": (_i64, [_i64]),
+    "rai_dqn_head_fwd": (C.c_int, [_vp] * 9 + [_i64, _i32, _i32, C.c_float] + [_vp] * 6 + [_i64, _vp]),
+    "rai_dqn_head_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "rai_argmax_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "rai_polyak_update": (C.c_int, [_vp, _vp, _i64, C.c_double, C.c_double, _vp]),
 }
 RAI_DP_UID_BYTES = 128
 EXPORTED = tuple(_SIGNATURES)
