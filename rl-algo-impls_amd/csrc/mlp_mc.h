@@ -1,5 +1,6 @@
 // Multi-CU fused PPO epoch for CartPole-class MLP actor-critics (in_dim <= 4, n_actions <= 2).
-// Included once, inside mlp_ppo.hip's anonymous namespace (shares MlpArgs and the helpers).
+// Included once, after ppo_row_loss.h and mlp_mc_common.h, inside mlp_ppo.hip's anonymous namespace
+// (shares MlpArgs, the row loss, the weight layout WL_* and the helpers).
 //
 // Why more than one CU per network: one CU per network is bound by its own MFMA pipe and by
 // the latency of a long dependent chain per minibatch (~33 us per minibatch at 256 rows).  Here
@@ -28,31 +29,9 @@ constexpr int MC_NT = 256;           // threads per CU (4 waves, one per SIMD)
 constexpr int MC_NW = MC_NT / 64;
 constexpr int MC_RC = 64;            // minibatch rows per CU (MC_NW 16-row tiles)
 constexpr int MC_GRID = 8 * MC_G;    // blocks launched; only b % 8 < 2 work
-
-// Weight layout shared by LDS, the partial-gradient buffers and the exchange slots (floats).
-constexpr int WL_W1 = 0;                   // [64][4]
-constexpr int WL_B1 = WL_W1 + HID * 4;     // [64]
-constexpr int WL_W2 = WL_B1 + HID;         // [64][LD]
-constexpr int WL_B2 = WL_W2 + HID * LD;    // [64]
-constexpr int WL_W3 = WL_B2 + HID;         // [OUTP][LD]
-constexpr int WL_N = 4752;                 // >= WL_W3 + 2 * LD + 8, multiple of 16
-constexpr int WL_CH = WL_N / 4;            // float4 chunks
-constexpr int MC_CPT = (WL_CH + MC_NT - 1) / MC_NT;  // chunks owned per thread
-constexpr int MC_SLOT = WL_N;
-static_assert(WL_W3 + 2 * LD + 8 <= WL_N, "weight layout");
-
-// Cross-GPU exchange region (one per rank, IPC-mapped by every other rank):
-//   [0, 2048)    u64 flags[2 nets][XDP_MAXW ranks][CUs per network]: step id of the last share pushed
-//   [2048, 2112) u64 self-test flags[XDP_MAXW ranks]
-//   [4096, ...)  floats slots[2 parities][world][2 nets][WL_N]: each rank's gradient of the step
-constexpr int XDP_MAXW = 8;
-constexpr int XDP_TEST_OFF = 2048;     // self-test flags
-constexpr int XDP_FLAGS_BYTES = 4096;  // slots start here
+constexpr int MC_SLOT = WL_N;        // floats per exchange slot (one partial gradient)
+static_assert(MC_CPT * MC_NT >= WL_CH, "chunks per thread");
 static_assert(2 * XDP_MAXW * MC_G * 8 <= XDP_TEST_OFF, "xdp flags");
-__host__ __device__ constexpr long long xdp_region_bytes(int world) {
-  return XDP_FLAGS_BYTES + 2LL * world * 2 * WL_N * (long long)sizeof(float);
-}
-constexpr int XDP_AUX = 17;  // sc0 | sc1: system-scope (cross-device) stores and loads
 
 // sync words (u64) at the start of the workspace, zeroed before every launch
 constexpr int MC_CNT = 0;     // [2 nets] arrival counters
@@ -79,87 +58,6 @@ struct SmemM {
   float Ps[MC_NW][OUTP + 6][HID];  // per-wave partials: dW3[o], db2, db1, dW1[k]
 };
 
-template <int OUTP>
-__device__ __forceinline__ int wl_b3() { return WL_W3 + OUTP * LD; }
-
-// weight-layout index -> flat torch parameters() index of this network (-1: padding).
-// Branch-free (every region computed, the right one selected): per-lane branches here split the
-// gathers that use it into separate basic blocks, each waiting for its own load.
-template <int OUTP>
-__device__ __forceinline__ int wl_to_flat(int e, int IN, int OUT, int base) {
-  const int fW1 = base, fb1 = fW1 + HID * IN, fW2 = fb1 + HID, fb2 = fW2 + HID * HID, fW3 = fb2 + HID,
-            fb3 = fW3 + OUT * HID;
-  constexpr int WL_B3 = WL_W3 + OUTP * LD;
-  const int j1 = e >> 2, k1 = e & 3;
-  const int r1 = k1 < IN ? fW1 + j1 * IN + k1 : -1;
-  const int r_b1 = fb1 + (e - WL_B1);
-  const int q2 = e - WL_W2, j2 = q2 / LD, k2 = q2 - j2 * LD;
-  const int r2 = k2 < HID ? fW2 + j2 * HID + k2 : -1;
-  const int r_b2 = fb2 + (e - WL_B2);
-  const int q3 = e - WL_W3, o3 = q3 / LD, k3 = q3 - o3 * LD;
-  const int r3 = (o3 < OUT && k3 < HID) ? fW3 + o3 * HID + k3 : -1;
-  const int o4 = e - WL_B3;
-  const int r4 = (o4 >= 0 && o4 < OUT) ? fb3 + o4 : -1;
-  int f = -1;
-  f = e < WL_B3 + 8 ? r4 : f;
-  f = e < WL_B3 ? r3 : f;
-  f = e < WL_W3 ? r_b2 : f;
-  f = e < WL_B2 ? r2 : f;
-  f = e < WL_W2 ? r_b1 : f;
-  f = e < WL_B1 ? r1 : f;
-  return f;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mc_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f4 as_f4(u4v v) { return __builtin_bit_cast(f4, v); }
-__device__ __forceinline__ u4v as_u4(f4 v) { return __builtin_bit_cast(u4v, v); }
-
-// Wave-wide sums on the VALU (DPP row butterflies + lane swaps) instead of ds_bpermute shuffles:
-// a fixed combination order in which every lane ends with the same bits (common.h wave_sum_dpp).
-__device__ __forceinline__ float wave_sum_v(float v) { return wave_sum_dpp(v); }
-__device__ __forceinline__ double wave_sum_v(double v) { return wave_sum_dpp(v); }
-
-// torch Adam step (m, v, denom = sqrt(v)/sqrt(bc2) + eps, p -= lr/bc1 * m/denom) with the
-// hardware sqrt / reciprocal (1 ulp each) instead of the IEEE-exact sequences: ~1e-7 relative
-// on the update, inside the fp32 tolerance the parity tests state.
-__device__ __forceinline__ void adam_update_fast(float& p, float& m, float& v, float g, float w1, float w2,
-                                                 float beta2, float inv_bc2_sqrt, float neg_step, float eps) {
-  m = m + w1 * (g - m);
-  v = v * beta2;
-  v = v + (w2 * g) * g;
-  const float denom = __builtin_amdgcn_sqrtf(v) * inv_bc2_sqrt + eps;
-  p = p + neg_step * (m * __builtin_amdgcn_rcpf(denom));
-}
-
-// The same update on an element pair in packed fp32 (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two
-// elements per VALU op; per element the identical IEEE operations, so identical results), the square
-// root and reciprocal per element.  The 8-CU epoch kernel's whole-network Adam is on every step's
-// critical path.
-typedef float f2a __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void adam_update_fast2(f2a& p, f2a& m, f2a& v, f2a g, float w1, float w2, float beta2,
-                                                  float inv_bc2_sqrt, float neg_step, float eps) {
-  const f2a W1 = {w1, w1}, W2 = {w2, w2}, B2 = {beta2, beta2}, IB = {inv_bc2_sqrt, inv_bc2_sqrt}, EP = {eps, eps},
-            NS = {neg_step, neg_step};
-  m = m + W1 * (g - m);
-  v = v * B2;
-  v = v + (W2 * g) * g;
-  const f2a sq = {__builtin_amdgcn_sqrtf(v.x), __builtin_amdgcn_sqrtf(v.y)};
-  const f2a denom = sq * IB + EP;
-  const f2a rc = {__builtin_amdgcn_rcpf(denom.x), __builtin_amdgcn_rcpf(denom.y)};
-  p = p + NS * (m * rc);
-}
-
-// Branch-free gather: the load is issued unconditionally (clamped index) and masked after, so
-// a run of them stays in one basic block with all loads in flight (a guarded load becomes a
-// branch, and the wait for its data is then placed before the next one is issued).
-__device__ __forceinline__ float ld_or0(const float* p, int f) {
-  const float v = p[f >= 0 ? f : 0];
-  return f >= 0 ? v : 0.f;
-}
-
 template <int OUTP, bool ACTOR, int RELU>
 __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const int c) {
   constexpr int net = ACTOR ? 0 : 1;
@@ -174,10 +72,7 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
   const int IN = a.in_dim;
   const int NA = a.n_act;
   const int OUT = ACTOR ? NA : 1;
-  const float clip_range = a.hp->clip_range, ent_coef = a.hp->ent_coef, vf_coef0 = a.hp->vf_coef[0];
-  const float clip_range_vf = a.hp->clip_range_vf;
-  const int has_vclip = a.hp->has_clip_range_vf, vf_fn = a.hp->vf_loss_fn;
-  const float halve = a.hp->ppo2_vf_coef_halving ? 0.5f : 1.f;
+  RowLossHp lh = row_loss_hp(a.hp, NA);
   const float beta2 = a.ohp->beta2, adam_eps = a.ohp->eps, lr = a.ohp->lr;
   const double beta1_d = a.ohp->beta1_d, beta2_d = a.ohp->beta2_d;
   const bool grads_mode = a.grad_out != nullptr;
@@ -247,8 +142,7 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
   const int64_t step0 = a.state->opt_step;
   const int stat0 = a.state->stat_index;
   const int norm0 = a.state->norm_index;
-  const int latched = a.state->pi_coef_zero;
-  const float pi_coef = latched ? 0.f : 1.f;
+  lh.pi_coef = a.state->pi_coef_zero ? 0.f : 1.f;
 
   int r_act = 0;
   float r_a = 0.f, r_b = 0.f, r_c = 0.f, r_d = 1.f, r_x = 0.f;
@@ -380,7 +274,7 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
     const int c_act = r_act;
     const float c_a = r_a, c_b = r_b, amean = r_c, aden = r_d, c_x = r_x;
     if (mb + 1 < mb_end) prefetch(mb + 1);
-    const float invB = 1.f / (float)(rows * a.world);
+    lh.invB = 1.f / (float)(rows * a.world);
     const int R = w * 16;               // first local row of this wave's tile
     const int RG = c * MC_RC + R;       // ... and its row within the minibatch
 
@@ -451,84 +345,11 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
         z[o] = sel + S.Wt[WL_B3 + o];
         dq[o] = 0.f;
       }
-      if (valid) {
-        if (ACTOR) {
-          float m = F32_MIN;
+      float sr[4] = {0.f, 0.f, 0.f, 0.f};
+      if (valid) ppo_row_loss<OUTP, ACTOR>(z, lh, c_act, c_a, c_b, ACTOR ? (c_b - amean) / aden : 0.f, dq, sr);
+      if (li < 4) {
 #pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) m = fmaxf(m, z[o]);
-          float se = 0.f;
-#pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) se += expf(z[o] - m);
-          const float lse = m + logf(se);
-          float H = 0.f;
-#pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) {
-              const float n = z[o] - lse;
-              H -= fmaxf(n, F32_MIN) * expf(n);
-            }
-          const int act = min(max(c_act, 0), NA - 1);
-          float zact = z[0];
-#pragma unroll
-          for (int o = 1; o < OUTP; ++o)
-            if (o == act) zact = z[o];
-          const float logp = zact - lse;
-          const float A = (c_b - amean) / aden;
-          const float logratio = logp - c_a;
-          const float ratio = expf(logratio);
-          const float lo = 1.f - clip_range, hi = 1.f + clip_range;
-          const float cr = fminf(fmaxf(ratio, lo), hi);
-          const float s1 = ratio * A, s2 = cr * A;
-          const float gpi = -pi_coef * invB;
-          float g1, g2;
-          if (s1 < s2) { g1 = gpi; g2 = 0.f; }
-          else if (s1 > s2) { g1 = 0.f; g2 = gpi; }
-          else { g1 = gpi * 0.5f; g2 = gpi * 0.5f; }
-          const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-          const float dlogp = (g1 * A + (g2 * A) * in_clip) * ratio;
-          const float dent = -ent_coef * invB;
-#pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) {
-              const float n = z[o] - lse;
-              const float p = expf(n);
-              dq[o] = dlogp * ((o == act ? 1.f : 0.f) - p) + dent * (-p * (n + H));
-            }
-          if (li < 4) {
-            st[0] = fminf(s1, s2);
-            st[1] = (ratio - 1.f) - logratio;
-            st[2] = (fabsf(ratio - 1.f) > clip_range) ? 1.f : 0.f;
-            st[3] = H;
-          }
-        } else {
-          const float v = z[0], Rt = c_b;
-          const float gl = (vf_coef0 * halve) * invB;
-          float l = vf_loss(vf_fn, v - Rt), dv;
-          float vcf = 0.f;
-          if (has_vclip) {
-            const float vc_ = clip_range_vf;
-            const float dvo = v - c_a;
-            const float vcl = c_a + fminf(fmaxf(dvo, -vc_), vc_);
-            const float l2 = vf_loss(vf_fn, vcl - Rt);
-            float w1, w2;
-            if (l > l2) { w1 = gl; w2 = 0.f; }
-            else if (l < l2) { w1 = 0.f; w2 = gl; }
-            else { w1 = gl * 0.5f; w2 = gl * 0.5f; }
-            const float inv = (dvo >= -vc_ && dvo <= vc_) ? 1.f : 0.f;
-            dv = w1 * vf_grad(vf_fn, v - Rt) + (w2 * vf_grad(vf_fn, vcl - Rt)) * inv;
-            vcf = (fabsf(v - c_a) > vc_) ? 1.f : 0.f;
-            l = fmaxf(l, l2);
-          } else {
-            dv = gl * vf_grad(vf_fn, v - Rt);
-          }
-          dq[0] = dv;
-          if (li < 4) {
-            st[0] = l;
-            st[1] = vcf;
-          }
-        }
+        for (int i = 0; i < 4; ++i) st[i] = sr[i];
       }
       float dr[4][OUTP];
 #pragma unroll
@@ -912,14 +733,14 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
       if (ACTOR) {
         const float pi_loss = (float)(-sv[0] / Bd);
         const float ent_loss = (float)(-sv[3] / Bd);
-        row[0] = pi_coef * pi_loss + ent_coef * ent_loss;  // host adds the value term
+        row[0] = lh.pi_coef * pi_loss + lh.ent_coef * ent_loss;  // host adds the value term
         row[1] = pi_loss;
         row[2] = ent_loss;
         row[3] = (float)(sv[1] / Bd);
         row[4] = (float)(sv[2] / Bd);
       } else {
-        row[5] = (float)(sv[0] / Bd) * halve;
-        row[5 + RAI_MAX_K] = has_vclip ? (float)(sv[1] / Bd) : 0.f;
+        row[5] = (float)(sv[0] / Bd) * lh.halve;
+        row[5 + RAI_MAX_K] = lh.has_vclip ? (float)(sv[1] / Bd) : 0.f;
       }
     }
   }

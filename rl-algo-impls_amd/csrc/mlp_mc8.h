@@ -1,7 +1,7 @@
 // Eight-CU-per-network fused PPO epoch for CartPole-class MLP actor-critics (in_dim <= 4,
 // n_actions <= 2): the default epoch kernel (single GPU and in-kernel cross-GPU exchange).
-// Included once, after mlp_mc.h, inside mlp_ppo.hip's anonymous namespace (shares MlpArgs, the
-// weight layout WL_* and the helpers).
+// Included once, after ppo_row_loss.h and mlp_mc_common.h, inside mlp_ppo.hip's anonymous namespace
+// (shares MlpArgs, the row loss, the weight layout WL_* and the helpers).
 //
 // Why 8 CUs and two exchange rounds.  With 4 CUs per network (mlp_mc.h) a minibatch step is ~65 %
 // wave-serial compute: each wave carries one 16-row tile through ~200 dependent MFMAs plus the
@@ -67,6 +67,7 @@ constexpr int64_t M8_S2_OFF = M8_S1_BYTES;                                  // [
 constexpr int64_t M8_SQ_OFF = M8_S2_OFF + 2LL * 2 * WL_N * sizeof(float);   // [par][net][c][hi, lo] share |g|^2 granules
 constexpr int64_t M8_SCRATCH = M8_SQ_OFF + 2LL * 2 * M8_GMAX * M8_NW * sizeof(double);
 static_assert(2 * XDP_MAXW * M8_GMAX * 8 <= XDP_TEST_OFF, "xdp share flags");
+static_assert(MC_CPT * M8_NT >= WL_CH, "chunks per thread");
 
 template <int OUTP, int G, int RCV>
 struct SmemM8 {
@@ -94,90 +95,6 @@ struct SmemM8 {
   float Zp[Geo::WPT][Geo::RC][OUTP];  // output-layer partial sums of the column parts
   float Ps[Geo::NTILE][OUTP + 6][HID];  // per-tile partials: dW3[o], db2, db1, dW1[k]
 };
-
-// Per-row PPO loss gradient (reference: rl_algo_impls/ppo/ppo.py:326-377) for one row's logits
-// (actor) or value (critic): dq = dLoss/dz, st = the row's statistics contributions.
-struct RowLossHp {
-  float clip_range, ent_coef, pi_coef, invB, vf_coef0, halve, clip_range_vf;
-  int has_vclip, vf_fn, NA;
-};
-template <int OUTP, bool ACTOR>
-__device__ __forceinline__ void ppo_row_loss(const float (&z)[OUTP], const RowLossHp& h, int c_act, float c_a,
-                                             float c_b, float A, float (&dq)[OUTP], float (&st)[4]) {
-  if (ACTOR) {
-    const int NA = h.NA;
-    float m = F32_MIN;
-#pragma unroll
-    for (int o = 0; o < OUTP; ++o)
-      if (o < NA) m = fmaxf(m, z[o]);
-    float se = 0.f;
-#pragma unroll
-    for (int o = 0; o < OUTP; ++o)
-      if (o < NA) se += expf(z[o] - m);
-    const float lse = m + logf(se);
-    float H = 0.f;
-#pragma unroll
-    for (int o = 0; o < OUTP; ++o)
-      if (o < NA) {
-        const float n = z[o] - lse;
-        H -= fmaxf(n, F32_MIN) * expf(n);
-      }
-    const int act = min(max(c_act, 0), NA - 1);
-    float zact = z[0];
-#pragma unroll
-    for (int o = 1; o < OUTP; ++o)
-      if (o == act) zact = z[o];
-    const float logp = zact - lse;
-    const float logratio = logp - c_a;
-    const float ratio = expf(logratio);
-    const float lo = 1.f - h.clip_range, hi = 1.f + h.clip_range;
-    const float cr = fminf(fmaxf(ratio, lo), hi);
-    const float s1 = ratio * A, s2 = cr * A;
-    const float gpi = -h.pi_coef * h.invB;
-    float g1, g2;
-    if (s1 < s2) { g1 = gpi; g2 = 0.f; }
-    else if (s1 > s2) { g1 = 0.f; g2 = gpi; }
-    else { g1 = gpi * 0.5f; g2 = gpi * 0.5f; }
-    const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-    const float dlogp = (g1 * A + (g2 * A) * in_clip) * ratio;
-    const float dent = -h.ent_coef * h.invB;
-#pragma unroll
-    for (int o = 0; o < OUTP; ++o)
-      if (o < NA) {
-        const float n = z[o] - lse;
-        const float p = expf(n);
-        dq[o] = dlogp * ((o == act ? 1.f : 0.f) - p) + dent * (-p * (n + H));
-      }
-    st[0] = fminf(s1, s2);
-    st[1] = (ratio - 1.f) - logratio;
-    st[2] = (fabsf(ratio - 1.f) > h.clip_range) ? 1.f : 0.f;
-    st[3] = H;
-  } else {
-    const float v = z[0], Rt = c_b;
-    const float gl = (h.vf_coef0 * h.halve) * h.invB;
-    float l = vf_loss(h.vf_fn, v - Rt), dv;
-    float vcf = 0.f;
-    if (h.has_vclip) {
-      const float vc_ = h.clip_range_vf;
-      const float dvo = v - c_a;
-      const float vcl = c_a + fminf(fmaxf(dvo, -vc_), vc_);
-      const float l2 = vf_loss(h.vf_fn, vcl - Rt);
-      float w1, w2;
-      if (l > l2) { w1 = gl; w2 = 0.f; }
-      else if (l < l2) { w1 = 0.f; w2 = gl; }
-      else { w1 = gl * 0.5f; w2 = gl * 0.5f; }
-      const float inv = (dvo >= -vc_ && dvo <= vc_) ? 1.f : 0.f;
-      dv = w1 * vf_grad(h.vf_fn, v - Rt) + (w2 * vf_grad(h.vf_fn, vcl - Rt)) * inv;
-      vcf = (fabsf(v - c_a) > vc_) ? 1.f : 0.f;
-      l = fmaxf(l, l2);
-    } else {
-      dv = gl * vf_grad(h.vf_fn, v - Rt);
-    }
-    dq[0] = dv;
-    st[0] = l;
-    st[1] = vcf;
-  }
-}
 
 // bounded spin of one lane until sync[i0] and sync[i1] both reach `want`
 __device__ __forceinline__ bool m8_wait2(unsigned long long* sync, int i0, int i1, unsigned long long want,
@@ -208,15 +125,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
   const int IN = a.in_dim;
   const int NA = a.n_act;
   const int OUT = ACTOR ? NA : 1;
-  RowLossHp lh;
-  lh.clip_range = a.hp->clip_range;
-  lh.ent_coef = a.hp->ent_coef;
-  lh.vf_coef0 = a.hp->vf_coef[0];
-  lh.clip_range_vf = a.hp->clip_range_vf;
-  lh.has_vclip = a.hp->has_clip_range_vf;
-  lh.vf_fn = a.hp->vf_loss_fn;
-  lh.halve = a.hp->ppo2_vf_coef_halving ? 0.5f : 1.f;
-  lh.NA = NA;
+  RowLossHp lh = row_loss_hp(a.hp, NA);
   float beta2 = a.ohp->beta2, adam_eps = a.ohp->eps;
   const float lr = a.ohp->lr;
   const double beta1_d = a.ohp->beta1_d, beta2_d = a.ohp->beta2_d;

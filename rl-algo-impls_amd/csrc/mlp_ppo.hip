@@ -51,7 +51,6 @@ constexpr int MAXOUT = 8;
 constexpr int MAXB = 256;
 constexpr int NT = 1024;
 constexpr int NW = NT / 64;
-constexpr float F32_MIN = -3.4028234663852886e38f;
 
 struct MlpArgs {
   float* params;
@@ -184,15 +183,7 @@ __device__ __forceinline__ float tanh_bf(float x) {
 __device__ __forceinline__ float act_f(const int relu, float z) { return relu ? fmaxf(z, 0.f) : tanh_bf(z); }
 __device__ __forceinline__ float act_d(int relu, float h) { return relu ? (h > 0.f ? 1.f : 0.f) : 1.f - h * h; }
 
-__device__ __forceinline__ float vf_loss(int fn, float x) {
-  if (fn == 0) return x * x;
-  const float z = fabsf(x);
-  return z < 1.f ? 0.5f * z * z : (z - 0.5f);
-}
-__device__ __forceinline__ float vf_grad(int fn, float x) {
-  if (fn == 0) return 2.f * x;
-  return x <= -1.f ? -1.f : (x >= 1.f ? 1.f : x);
-}
+#include "ppo_row_loss.h"
 
 // Sum over the 16 lanes of a DPP row; every lane of the row receives the same bits.
 template <int CTRL>
@@ -253,10 +244,7 @@ __device__ __forceinline__ void mlp_net(const MlpArgs& a, Smem<INP, OUTP>& S) {
   const int NA = a.n_act;
   const int OUT = ACTOR ? NA : 1;
   constexpr int relu = RELU;  // compile-time: keeps the activation epilogues in one basic block
-  const float clip_range = a.hp->clip_range, ent_coef = a.hp->ent_coef, vf_coef0 = a.hp->vf_coef[0];
-  const float clip_range_vf = a.hp->clip_range_vf;
-  const int has_vclip = a.hp->has_clip_range_vf, vf_fn = a.hp->vf_loss_fn;
-  const float halve = a.hp->ppo2_vf_coef_halving ? 0.5f : 1.f;
+  RowLossHp lh = row_loss_hp(a.hp, NA);
   const float beta2 = a.ohp->beta2, adam_eps = a.ohp->eps, lr = a.ohp->lr;
   const double beta1_d = a.ohp->beta1_d, beta2_d = a.ohp->beta2_d;
   const bool grads_mode = a.grad_out != nullptr;
@@ -323,8 +311,7 @@ __device__ __forceinline__ void mlp_net(const MlpArgs& a, Smem<INP, OUTP>& S) {
   const int64_t step0 = a.state->opt_step;
   const int stat0 = a.state->stat_index;
   const int norm0 = a.state->norm_index;
-  const int latched = a.state->pi_coef_zero;
-  const float pi_coef = latched ? 0.f : 1.f;
+  lh.pi_coef = a.state->pi_coef_zero ? 0.f : 1.f;
 
   // ---- per-minibatch inputs, prefetched into registers one minibatch ahead ------------------
   // thread t < rows: row t's (action, old logp, adv | old value, return);
@@ -385,7 +372,7 @@ __device__ __forceinline__ void mlp_net(const MlpArgs& a, Smem<INP, OUTP>& S) {
       for (int q = 0; q < NQ; ++q) cx[c][q] = px[c][q];
     const float amean = r_c, aden = r_d;
     if (mb + 1 < mb_end) prefetch(mb + 1);
-    const float invB = 1.f / (float)(rows * a.world);
+    lh.invB = 1.f / (float)(rows * a.world);
 
     // per-thread partial gradients over this minibatch's rows
     f4 gw2 = {0.f, 0.f, 0.f, 0.f};   // dW2 tile (MFMA accumulator)
@@ -478,77 +465,10 @@ __device__ __forceinline__ void mlp_net(const MlpArgs& a, Smem<INP, OUTP>& S) {
             float z[OUTP];
 #pragma unroll
             for (int o = 0; o < OUTP; ++o) z[o] = (S.outp[0][s][o] + S.outp[1][s][o]) + S.b3[o];
-            if (ACTOR) {
-              float m = F32_MIN;
+            float sr[4] = {0.f, 0.f, 0.f, 0.f};
+            ppo_row_loss<OUTP, ACTOR>(z, lh, c_act, c_a, c_b, ACTOR ? (c_b - amean) / aden : 0.f, d, sr);
 #pragma unroll
-              for (int o = 0; o < OUTP; ++o)
-                if (o < NA) m = fmaxf(m, z[o]);
-              float se = 0.f;
-#pragma unroll
-              for (int o = 0; o < OUTP; ++o)
-                if (o < NA) se += expf(z[o] - m);
-              const float lse = m + logf(se);
-              float H = 0.f;
-#pragma unroll
-              for (int o = 0; o < OUTP; ++o)
-                if (o < NA) {
-                  const float n = z[o] - lse;
-                  H -= fmaxf(n, F32_MIN) * expf(n);
-                }
-              const int act = min(max(c_act, 0), NA - 1);
-              float zact = z[0];
-#pragma unroll
-              for (int o = 1; o < OUTP; ++o)
-                if (o == act) zact = z[o];
-              const float logp = zact - lse;
-              const float A = (c_b - amean) / aden;
-              const float logratio = logp - c_a;
-              const float ratio = expf(logratio);
-              const float lo = 1.f - clip_range, hi = 1.f + clip_range;
-              const float cr = fminf(fmaxf(ratio, lo), hi);
-              const float s1 = ratio * A, s2 = cr * A;
-              const float gpi = -pi_coef * invB;
-              float g1, g2;
-              if (s1 < s2) { g1 = gpi; g2 = 0.f; }
-              else if (s1 > s2) { g1 = 0.f; g2 = gpi; }
-              else { g1 = gpi * 0.5f; g2 = gpi * 0.5f; }
-              const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-              const float dlogp = (g1 * A + (g2 * A) * in_clip) * ratio;
-              const float dent = -ent_coef * invB;
-#pragma unroll
-              for (int o = 0; o < OUTP; ++o)
-                if (o < NA) {
-                  const float n = z[o] - lse;
-                  const float p = expf(n);
-                  d[o] = dlogp * ((o == act ? 1.f : 0.f) - p) + dent * (-p * (n + H));
-                }
-              st[0] += fminf(s1, s2);
-              st[1] += (ratio - 1.f) - logratio;
-              st[2] += (fabsf(ratio - 1.f) > clip_range) ? 1.f : 0.f;
-              st[3] += H;
-            } else {
-              const float v = z[0], R = c_b;
-              const float gl = (vf_coef0 * halve) * invB;
-              float l = vf_loss(vf_fn, v - R), dv;
-              if (has_vclip) {
-                const float vc_ = clip_range_vf;
-                const float dvo = v - c_a;
-                const float vcl = c_a + fminf(fmaxf(dvo, -vc_), vc_);
-                const float l2 = vf_loss(vf_fn, vcl - R);
-                float w1, w2;
-                if (l > l2) { w1 = gl; w2 = 0.f; }
-                else if (l < l2) { w1 = 0.f; w2 = gl; }
-                else { w1 = gl * 0.5f; w2 = gl * 0.5f; }
-                const float inv = (dvo >= -vc_ && dvo <= vc_) ? 1.f : 0.f;
-                dv = w1 * vf_grad(vf_fn, v - R) + (w2 * vf_grad(vf_fn, vcl - R)) * inv;
-                st[1] += (fabsf(v - c_a) > vc_) ? 1.f : 0.f;
-                l = fmaxf(l, l2);
-              } else {
-                dv = gl * vf_grad(vf_fn, v - R);
-              }
-              st[0] += l;
-              d[0] = dv;
-            }
+            for (int i = 0; i < (ACTOR ? 4 : 2); ++i) st[i] += sr[i];
           }
 #pragma unroll
           for (int o = 0; o < OUTP; ++o) {
@@ -741,14 +661,14 @@ __device__ __forceinline__ void mlp_net(const MlpArgs& a, Smem<INP, OUTP>& S) {
         if (ACTOR) {
           const float pi_loss = (float)(-sv[0] / Bd);
           const float ent_loss = (float)(-sv[3] / Bd);
-          row[0] = pi_coef * pi_loss + ent_coef * ent_loss;  // host adds the value term
+          row[0] = lh.pi_coef * pi_loss + lh.ent_coef * ent_loss;  // host adds the value term
           row[1] = pi_loss;
           row[2] = ent_loss;
           row[3] = (float)(sv[1] / Bd);
           row[4] = (float)(sv[2] / Bd);
         } else {
-          row[5] = (float)(sv[0] / Bd) * halve;
-          row[5 + RAI_MAX_K] = has_vclip ? (float)(sv[1] / Bd) : 0.f;
+          row[5] = (float)(sv[0] / Bd) * lh.halve;
+          row[5 + RAI_MAX_K] = lh.has_vclip ? (float)(sv[1] / Bd) : 0.f;
         }
       }
       if (!grads_mode) {
@@ -922,10 +842,7 @@ __device__ __forceinline__ void mlp_rows(const MlpArgs& a, SmemR<OUTP>& S) {
   const int IN = a.in_dim;
   const int NA = a.n_act;
   const int OUT = ACTOR ? NA : 1;
-  const float clip_range = a.hp->clip_range, ent_coef = a.hp->ent_coef, vf_coef0 = a.hp->vf_coef[0];
-  const float clip_range_vf = a.hp->clip_range_vf;
-  const int has_vclip = a.hp->has_clip_range_vf, vf_fn = a.hp->vf_loss_fn;
-  const float halve = a.hp->ppo2_vf_coef_halving ? 0.5f : 1.f;
+  RowLossHp lh = row_loss_hp(a.hp, NA);
   const float beta2 = a.ohp->beta2, adam_eps = a.ohp->eps, lr = a.ohp->lr;
   const double beta1_d = a.ohp->beta1_d, beta2_d = a.ohp->beta2_d;
   const bool grads_mode = a.grad_out != nullptr;
@@ -982,8 +899,7 @@ __device__ __forceinline__ void mlp_rows(const MlpArgs& a, SmemR<OUTP>& S) {
   const int64_t step0 = a.state->opt_step;
   const int stat0 = a.state->stat_index;
   const int norm0 = a.state->norm_index;
-  const int latched = a.state->pi_coef_zero;
-  const float pi_coef = latched ? 0.f : 1.f;
+  lh.pi_coef = a.state->pi_coef_zero ? 0.f : 1.f;
 
   // ---- per-minibatch inputs, prefetched into registers one minibatch ahead ------------------
   // lane (g, li) of wave w: the loss inputs of row 16w + 4g + (li & 3) and the layer-1 MFMA
@@ -1034,7 +950,7 @@ __device__ __forceinline__ void mlp_rows(const MlpArgs& a, SmemR<OUTP>& S) {
     const int c_act = r_act;
     const float c_a = r_a, c_b = r_b, amean = r_c, aden = r_d, c_x = r_x;
     if (mb + 1 < mb_end) prefetch(mb + 1);
-    const float invB = 1.f / (float)(rows * a.world);
+    lh.invB = 1.f / (float)(rows * a.world);
     const int R = w * 16;  // first row of this wave's tile
 
     // ============ P_A: wave-local forward, loss and backward of rows [R, R + 16) ============
@@ -1111,84 +1027,11 @@ __device__ __forceinline__ void mlp_rows(const MlpArgs& a, SmemR<OUTP>& S) {
         z[o] = sel + S.b3[o];
         dq[o] = 0.f;
       }
-      if (valid) {
-        if (ACTOR) {
-          float m = F32_MIN;
+      float sr[4] = {0.f, 0.f, 0.f, 0.f};
+      if (valid) ppo_row_loss<OUTP, ACTOR>(z, lh, c_act, c_a, c_b, ACTOR ? (c_b - amean) / aden : 0.f, dq, sr);
+      if (li < 4) {
 #pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) m = fmaxf(m, z[o]);
-          float se = 0.f;
-#pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) se += expf(z[o] - m);
-          const float lse = m + logf(se);
-          float H = 0.f;
-#pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) {
-              const float n = z[o] - lse;
-              H -= fmaxf(n, F32_MIN) * expf(n);
-            }
-          const int act = min(max(c_act, 0), NA - 1);
-          float zact = z[0];
-#pragma unroll
-          for (int o = 1; o < OUTP; ++o)
-            if (o == act) zact = z[o];
-          const float logp = zact - lse;
-          const float A = (c_b - amean) / aden;
-          const float logratio = logp - c_a;
-          const float ratio = expf(logratio);
-          const float lo = 1.f - clip_range, hi = 1.f + clip_range;
-          const float cr = fminf(fmaxf(ratio, lo), hi);
-          const float s1 = ratio * A, s2 = cr * A;
-          const float gpi = -pi_coef * invB;
-          float g1, g2;
-          if (s1 < s2) { g1 = gpi; g2 = 0.f; }
-          else if (s1 > s2) { g1 = 0.f; g2 = gpi; }
-          else { g1 = gpi * 0.5f; g2 = gpi * 0.5f; }
-          const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-          const float dlogp = (g1 * A + (g2 * A) * in_clip) * ratio;
-          const float dent = -ent_coef * invB;
-#pragma unroll
-          for (int o = 0; o < OUTP; ++o)
-            if (o < NA) {
-              const float n = z[o] - lse;
-              const float p = expf(n);
-              dq[o] = dlogp * ((o == act ? 1.f : 0.f) - p) + dent * (-p * (n + H));
-            }
-          if (li < 4) {
-            st[0] = fminf(s1, s2);
-            st[1] = (ratio - 1.f) - logratio;
-            st[2] = (fabsf(ratio - 1.f) > clip_range) ? 1.f : 0.f;
-            st[3] = H;
-          }
-        } else {
-          const float v = z[0], Rt = c_b;
-          const float gl = (vf_coef0 * halve) * invB;
-          float l = vf_loss(vf_fn, v - Rt), dv;
-          float vcf = 0.f;
-          if (has_vclip) {
-            const float vc_ = clip_range_vf;
-            const float dvo = v - c_a;
-            const float vcl = c_a + fminf(fmaxf(dvo, -vc_), vc_);
-            const float l2 = vf_loss(vf_fn, vcl - Rt);
-            float w1, w2;
-            if (l > l2) { w1 = gl; w2 = 0.f; }
-            else if (l < l2) { w1 = 0.f; w2 = gl; }
-            else { w1 = gl * 0.5f; w2 = gl * 0.5f; }
-            const float inv = (dvo >= -vc_ && dvo <= vc_) ? 1.f : 0.f;
-            dv = w1 * vf_grad(vf_fn, v - Rt) + (w2 * vf_grad(vf_fn, vcl - Rt)) * inv;
-            vcf = (fabsf(v - c_a) > vc_) ? 1.f : 0.f;
-            l = fmaxf(l, l2);
-          } else {
-            dv = gl * vf_grad(vf_fn, v - Rt);
-          }
-          dq[0] = dv;
-          if (li < 4) {
-            st[0] = l;
-            st[1] = vcf;
-          }
-        }
+        for (int i = 0; i < 4; ++i) st[i] = sr[i];
       }
       // dL/d(out) of the 4 rows of this lane's D-layout: quad broadcast from lane r of each quad
       float dr[4][OUTP];
@@ -1378,14 +1221,14 @@ __device__ __forceinline__ void mlp_rows(const MlpArgs& a, SmemR<OUTP>& S) {
         if (ACTOR) {
           const float pi_loss = (float)(-sv[0] / Bd);
           const float ent_loss = (float)(-sv[3] / Bd);
-          row[0] = pi_coef * pi_loss + ent_coef * ent_loss;  // host adds the value term
+          row[0] = lh.pi_coef * pi_loss + lh.ent_coef * ent_loss;  // host adds the value term
           row[1] = pi_loss;
           row[2] = ent_loss;
           row[3] = (float)(sv[1] / Bd);
           row[4] = (float)(sv[2] / Bd);
         } else {
-          row[5] = (float)(sv[0] / Bd) * halve;
-          row[5 + RAI_MAX_K] = has_vclip ? (float)(sv[1] / Bd) : 0.f;
+          row[5] = (float)(sv[0] / Bd) * lh.halve;
+          row[5 + RAI_MAX_K] = lh.has_vclip ? (float)(sv[1] / Bd) : 0.f;
         }
       }
       if (!grads_mode) {
@@ -1517,6 +1360,7 @@ __global__ __launch_bounds__(NT) void mlp_ppo_rows_kernel(const MlpArgs a) {
   else mlp_rows<1, false, RELU>(a, *reinterpret_cast<SmemR<1>*>(smem_raw));
 }
 
+#include "mlp_mc_common.h"
 #include "mlp_mc.h"
 #include "mlp_mc8.h"
 
@@ -1528,10 +1372,10 @@ __global__ __launch_bounds__(NT) void mlp_ppo_epoch_kernel(const MlpArgs a) {
   else mlp_net<INP, 1, false, RELU>(a, *reinterpret_cast<Smem<INP, 1>*>(smem_raw));
 }
 
-template <int INP, int NAP>
-void launch_epoch(const MlpArgs& a, hipStream_t s) {
-  if (a.act_fn == 1) hipLaunchKernelGGL((mlp_ppo_epoch_kernel<INP, NAP, 1>), dim3(2), dim3(NT), 0, s, a);
-  else hipLaunchKernelGGL((mlp_ppo_epoch_kernel<INP, NAP, 0>), dim3(2), dim3(NT), 0, s, a);
+// Launch the ReLU (act_fn 1) or tanh instantiation of an epoch kernel
+template <typename K>
+void launch_act(const MlpArgs& a, K relu_kernel, K tanh_kernel, int grid, int threads, hipStream_t s) {
+  hipLaunchKernelGGL(a.act_fn == 1 ? relu_kernel : tanh_kernel, dim3(grid), dim3(threads), 0, s, a);
 }
 
 }  // namespace
@@ -1580,6 +1424,24 @@ int64_t statp_bytes(int64_t n_rows, int32_t batch_size) {
   return 2 * num_minibatches(n_rows, batch_size) * (MC_G > M8_GMAX ? MC_G : M8_GMAX) * 4 * (int64_t)sizeof(double);
 }
 
+// The fields every entry point fills the same way: an epoch over all minibatches on one GPU with
+// advantage moments computed here (each entry point then sets what differs)
+MlpArgs mlp_args(float* params, float* exp_avg, float* exp_avg_sq, const float* obs, const int64_t* actions,
+                 const float* old_logp, const float* old_values, const float* advantages, const float* returns,
+                 int32_t in_dim, int32_t n_actions, int32_t activation, const rai_ppo_hparams* hp,
+                 const rai_optim_hparams* ohp, rai_train_state* state, float* stats, int32_t max_stats, float* norms,
+                 int32_t max_norms) {
+  MlpArgs a = {};
+  a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
+  a.obs = obs; a.actions = actions; a.old_logp = old_logp; a.old_values = old_values;
+  a.adv = advantages; a.ret = returns;
+  a.in_dim = in_dim; a.n_act = n_actions; a.act_fn = activation;
+  a.hp = hp; a.ohp = ohp; a.state = state;
+  a.stats = stats; a.max_stats = max_stats; a.norms = norms; a.max_norms = max_norms;
+  a.mb_begin = 0; a.mb_count = 1 << 30; a.world = 1;
+  return a;
+}
+
 int mlp_launch(MlpArgs& a, int32_t hidden, int32_t batch_size, int64_t n_rows, void* workspace,
                int64_t workspace_bytes, void* stream) {
   if (hidden != HID || a.in_dim < 1 || a.in_dim > MAXIN || a.n_act < 1 || a.n_act > MAXOUT ||
@@ -1618,27 +1480,22 @@ int mlp_launch(MlpArgs& a, int32_t hidden, int32_t batch_size, int64_t n_rows, v
     // multi-CU layout, G CUs per network: reduce-scatter + all-gather per minibatch
     if (mlp_cus_per_net() == 16 && batch_size <= 128 && mlp_per_rank_geometry()) {
       // <= 128 rows (256 / world per rank at world 2): 8 CUs of 16 rows, not 16 CUs of which half hold no rows
-      if (a.act_fn == 1) hipLaunchKernelGGL((mlp_ppo_mc8_kernel<1, 8, 16>), dim3(M8Geo<8, 16>::GRID), dim3(M8_NT), 0, s, a);
-      else hipLaunchKernelGGL((mlp_ppo_mc8_kernel<0, 8, 16>), dim3(M8Geo<8, 16>::GRID), dim3(M8_NT), 0, s, a);
+      launch_act(a, mlp_ppo_mc8_kernel<1, 8, 16>, mlp_ppo_mc8_kernel<0, 8, 16>, M8Geo<8, 16>::GRID, M8_NT, s);
     } else if (mlp_cus_per_net() == 16) {
-      if (a.act_fn == 1) hipLaunchKernelGGL((mlp_ppo_mc8_kernel<1, 16>), dim3(M8Geo<16>::GRID), dim3(M8_NT), 0, s, a);
-      else hipLaunchKernelGGL((mlp_ppo_mc8_kernel<0, 16>), dim3(M8Geo<16>::GRID), dim3(M8_NT), 0, s, a);
+      launch_act(a, mlp_ppo_mc8_kernel<1, 16>, mlp_ppo_mc8_kernel<0, 16>, M8Geo<16>::GRID, M8_NT, s);
     } else {
-      if (a.act_fn == 1) hipLaunchKernelGGL((mlp_ppo_mc8_kernel<1, 8>), dim3(M8Geo<8>::GRID), dim3(M8_NT), 0, s, a);
-      else hipLaunchKernelGGL((mlp_ppo_mc8_kernel<0, 8>), dim3(M8Geo<8>::GRID), dim3(M8_NT), 0, s, a);
+      launch_act(a, mlp_ppo_mc8_kernel<1, 8>, mlp_ppo_mc8_kernel<0, 8>, M8Geo<8>::GRID, M8_NT, s);
     }
   } else if (a.in_dim <= 4 && a.n_act <= 2 && (layout == 0 || layout == 3)) {
     // multi-CU layout, MC_G CUs per network, partial-gradient all-reduce per minibatch
-    if (a.act_fn == 1) hipLaunchKernelGGL((mlp_ppo_mc_kernel<1>), dim3(MC_GRID), dim3(MC_NT), 0, s, a);
-    else hipLaunchKernelGGL((mlp_ppo_mc_kernel<0>), dim3(MC_GRID), dim3(MC_NT), 0, s, a);
+    launch_act(a, mlp_ppo_mc_kernel<1>, mlp_ppo_mc_kernel<0>, MC_GRID, MC_NT, s);
   } else if (a.in_dim <= 4 && a.n_act <= 2 && layout == 1) {
     // row-tile layout on one CU per network (one pass over <= 256 rows)
-    if (a.act_fn == 1) hipLaunchKernelGGL((mlp_ppo_rows_kernel<1>), dim3(2), dim3(NT), 0, s, a);
-    else hipLaunchKernelGGL((mlp_ppo_rows_kernel<0>), dim3(2), dim3(NT), 0, s, a);
+    launch_act(a, mlp_ppo_rows_kernel<1>, mlp_ppo_rows_kernel<0>, 2, NT, s);
   } else if (a.in_dim <= 4 && a.n_act <= 2) {
-    launch_epoch<4, 2>(a, s);
+    launch_act(a, mlp_ppo_epoch_kernel<4, 2, 1>, mlp_ppo_epoch_kernel<4, 2, 0>, 2, NT, s);
   } else {
-    launch_epoch<8, 8>(a, s);
+    launch_act(a, mlp_ppo_epoch_kernel<8, 8, 1>, mlp_ppo_epoch_kernel<8, 8, 0>, 2, NT, s);
   }
   RAI_LAUNCH_CHECK();
   return RAI_OK;
@@ -1665,16 +1522,8 @@ extern "C" int rai_mlp_ppo_epoch(float* params, float* exp_avg, float* exp_avg_s
                                    1, hp, ohp, state, stats, max_stats, norms, max_norms, nullptr, workspace,
                                    workspace_bytes, rai_stream(stream));
   }
-  MlpArgs a = {};
-  a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-  a.obs = obs; a.actions = actions; a.old_logp = old_logp; a.old_values = old_values;
-  a.adv = advantages; a.ret = returns;
-  a.in_dim = in_dim; a.n_act = n_actions; a.act_fn = activation;
-  a.hp = hp; a.ohp = ohp; a.state = state;
-  a.stats = stats; a.max_stats = max_stats; a.norms = norms; a.max_norms = max_norms;
-  a.grad_out = nullptr; a.moments = nullptr;
-  a.mb_begin = 0; a.mb_count = 1 << 30; a.world = 1;
-  a.grad_in = nullptr; a.P_total = 0; a.sync_base = 0;
+  MlpArgs a = mlp_args(params, exp_avg, exp_avg_sq, obs, actions, old_logp, old_values, advantages, returns, in_dim,
+                       n_actions, activation, hp, ohp, state, stats, max_stats, norms, max_norms);
   return mlp_launch(a, hidden, batch_size, n_rows, workspace, workspace_bytes, stream);
 }
 
@@ -1698,16 +1547,9 @@ extern "C" int rai_mlp_ppo_epoch_xdp(float* params, float* exp_avg, float* exp_a
                                    workspace_bytes, rai_stream(stream), &x);
   }
   if (!(in_dim <= 4 && n_actions <= 2 && (mlp_layout() == 0 || mlp_layout() == 3))) return RAI_E_UNSUPPORTED;
-  MlpArgs a = {};
-  a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-  a.obs = obs; a.actions = actions; a.old_logp = old_logp; a.old_values = old_values;
-  a.adv = advantages; a.ret = returns;
-  a.in_dim = in_dim; a.n_act = n_actions; a.act_fn = activation;
-  a.hp = hp; a.ohp = ohp; a.state = state;
-  a.stats = stats; a.max_stats = max_stats; a.norms = norms; a.max_norms = max_norms;
-  a.grad_out = nullptr; a.moments = moments;
-  a.mb_begin = 0; a.mb_count = 1 << 30; a.world = world;
-  a.grad_in = nullptr; a.P_total = 0; a.sync_base = 0;
+  MlpArgs a = mlp_args(params, exp_avg, exp_avg_sq, obs, actions, old_logp, old_values, advantages, returns, in_dim,
+                       n_actions, activation, hp, ohp, state, stats, max_stats, norms, max_norms);
+  a.moments = moments; a.world = world;
   a.xpeers = peers; a.xrank = rank; a.xworld = world; a.xbase = step_base;
   return mlp_launch(a, hidden, batch_size, n_rows, workspace, workspace_bytes, stream);
 }
@@ -1780,13 +1622,8 @@ int rai_mlp_ppo_dp_step(float* params, float* exp_avg, float* exp_avg_sq, const 
     return RAI_E_UNSUPPORTED;
   if (!grad_out || !moments || !exp_avg || !exp_avg_sq) return RAI_E_NULLPTR;
   if (mb < 0 || mb_count < 0 || sync_base < 0) return RAI_E_SHAPE;
-  MlpArgs a = {};
-  a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-  a.obs = obs; a.actions = actions; a.old_logp = old_logp; a.old_values = old_values;
-  a.adv = advantages; a.ret = returns;
-  a.in_dim = in_dim; a.n_act = n_actions; a.act_fn = activation;
-  a.hp = hp; a.ohp = ohp; a.state = state;
-  a.stats = stats; a.max_stats = max_stats; a.norms = norms; a.max_norms = max_norms;
+  MlpArgs a = mlp_args(params, exp_avg, exp_avg_sq, obs, actions, old_logp, old_values, advantages, returns, in_dim,
+                       n_actions, activation, hp, ohp, state, stats, max_stats, norms, max_norms);
   a.grad_out = grad_out; a.moments = moments;
   a.mb_begin = mb; a.mb_count = mb_count; a.world = world;
   a.grad_in = grad_in; a.P_total = P_total; a.sync_base = sync_base;
@@ -1811,14 +1648,9 @@ extern "C" int rai_mlp_ppo_grads(const float* params, const float* obs, const in
                                    mb_count, moments, world, hp, ohp, state, stats, max_stats, nullptr, 0, grad_out,
                                    workspace, workspace_bytes, rai_stream(stream));
   }
-  MlpArgs a = {};
-  a.grad_in = nullptr; a.P_total = 0; a.sync_base = 0;
-  a.params = const_cast<float*>(params);
-  a.obs = obs; a.actions = actions; a.old_logp = old_logp; a.old_values = old_values;
-  a.adv = advantages; a.ret = returns;
-  a.in_dim = in_dim; a.n_act = n_actions; a.act_fn = activation;
-  a.hp = hp; a.ohp = ohp; a.state = state;
-  a.stats = stats; a.max_stats = max_stats; a.norms = nullptr; a.max_norms = 0;
+  // no optimizer state and no norms: the caller all-reduces grad_out and runs rai_clip_optim_step
+  MlpArgs a = mlp_args(const_cast<float*>(params), nullptr, nullptr, obs, actions, old_logp, old_values, advantages,
+                       returns, in_dim, n_actions, activation, hp, ohp, state, stats, max_stats, nullptr, 0);
   a.grad_out = grad_out; a.moments = moments;
   a.mb_begin = mb_begin; a.mb_count = mb_count; a.world = world;
   return mlp_launch(a, hidden, batch_size, n_rows, workspace, workspace_bytes, stream);

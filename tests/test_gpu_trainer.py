@@ -479,16 +479,26 @@ def _random_rollout(T, N, d, n, seed):
     (4, 2, "tanh", 256, 8, 96, "chunk"),     # chunked one-CU layout
     (6, 3, "tanh", 128, 8, 64, "chunk"),     # Acrobot-like: generic (8, 8) instantiation
     (8, 8, "relu", 256, 4, 200, "chunk"),    # maximum shape of the chunked kernel
+    # value clipping (layout + "+vclip": clip_range_vf = 0.2): the critic's clipped branch and its use of
+    # the old value, once per layout
+    (4, 2, "tanh", 40, 5, 50, "mc+vclip"),
+    (4, 2, "tanh", 40, 5, 50, "mc8+vclip"),
+    (4, 2, "tanh", 40, 5, 50, "mc4+vclip"),
+    (4, 2, "tanh", 40, 5, 50, "rows+vclip"),
+    (4, 2, "tanh", 40, 5, 50, "chunk+vclip"),
+    (6, 3, "tanh", 128, 8, 64, "chunk+vclip"),
 ])
 def test_fused_epoch_matches_generic_path(d, n, act, bs, T, N, layout, monkeypatch):
     """One epoch of the fused kernel (given layout; "mc" = the default, 16 CUs per network) vs
     the per-minibatch PyTorch path, same
-    rollout and permutation.  fp32 tolerances: different summation orders and the fused
-    kernel's hardware sqrt/rcp Adam."""
+    rollout and permutation ("+vclip": with value clipping).  fp32 tolerances: different summation
+    orders and the fused kernel's hardware sqrt/rcp Adam."""
     from rl_algo_impls_amd.policy import ActorCritic
 
     if (T * N) % bs == 1:
         pytest.skip("1-row minibatch has no unbiased std")
+    layout, _, vclip = layout.partition("+")
+    clip_range_vf = 0.2 if vclip else None
     if layout == "mc8":
         monkeypatch.setenv("RAI_MLP_CUS", "8")
     elif layout != "mc":
@@ -499,7 +509,7 @@ def test_fused_epoch_matches_generic_path(d, n, act, bs, T, N, layout, monkeypat
         torch.manual_seed(5)
         policy = ActorCritic(_SpaceEnv(d, n), activation_fn=act).to(DEV)
         algo = PPO(policy, DEV, None, batch_size=bs, n_epochs=2, learning_rate=3e-3, ent_coef=0.01,
-                   clip_range=0.2, gamma=0.98, gae_lambda=0.9)
+                   clip_range=0.2, clip_range_vf=clip_range_vf, gamma=0.98, gae_lambda=0.9)
         algo.force_generic = generic
         assert (algo.fused_mlp_spec() is None) == generic
         obs, a_, rew, starts, vals, logp, nstarts, nvals = roll
