@@ -909,6 +909,52 @@ int rai_argmax_rows(const float* x, int64_t B, int32_t A, int64_t* out, void* st
 int rai_polyak_update(float* target, const float* params, int64_t n, double tau, double one_minus_tau,
                       void* stream);
 
+/* --------------------------------------------------------------------------
+ * gSDE actor head (use_sde, squash_output; csrc/sde.hip, csrc/sde_row.h).  Replaces
+ * rl_algo_impls/shared/actor/state_dependent_noise.py:35-78,140-199 (distribution, log_prob, entropy,
+ * sample, sample_weights) and the squash branch of clamp_actions (actor_critic.py:62-87).
+ * All f32.  latent (B, H): the actor's last hidden activation (no gradient flows into it here: learn_std is
+ * never set); mu (B, A); log_std (H, A) when full_std, else (H, 1); S = exp(log_std).
+ *   sigma[b, a] = sqrt(sum_h latent[b, h]^2 S[h, a]^2 + 1e-6)
+ *   g = a, or atanh(clamp(a, -1 + eps, 1 - eps)) when squash (eps = float32 machine epsilon)
+ *   logp[b]    = sum_a [-(g - mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi)]
+ *                - (squash) sum_a log(1 - tanh(g)^2 + 1e-6)
+ *   entropy[b] = sum_a [1/2 + log sqrt(2 pi) + log sigma], or -logp[b] when squash
+ * Sums are carried in double in a fixed order and rounded once.  Supported: 1 <= H <= 512, 1 <= A <= 32
+ * (else RAI_E_UNSUPPORTED: the caller takes the torch formula).
+ *
+ * rai_sde_head_fwd writes logp (B), entropy (B) and sigma (B, A), which the backward reads.
+ * rai_sde_head_bwd, from d_logp (B) and d_entropy (B): d_mu (B, A) and
+ *   d_log_std[h, a] = sum_b d_var[b, a] latent[b, h]^2 2 S[h, a]^2  (summed over a as well when !full_std),
+ * the batch sum in ascending b (two calls give the same bits; no atomics).  d_log_std is written
+ * (accumulate == 0) or added to (accumulate != 0: the flat .grad view).
+ *
+ * rai_sde_sample_weights fills the per-env exploration matrices E (N, H, A) and the shared E0 (H, A) with
+ * S[h, a] * eps, eps standard normal: Philox4x32-10 with key seed and counter (offset, flat element / 4),
+ * Box-Muller; E0 continues E's flat index, so no two elements share a draw.
+ *
+ * rai_sde_sample, per row n: x = mu[n] + latent[n] . E[n] (e_stride: floats between consecutive rows'
+ * matrices; 0 = the one matrix at E for every row), actions_out = tanh(x) when squash else x; clamped_out
+ * (may be NULL) = clip(a, low, high), or low + 0.5 (a + 1) (high - low) when squash (low / high (A), required
+ * then); logp_out of the stored action by the same device function as rai_sde_head_fwd (bit-identical);
+ * v_out (N, K) = v_in when both are given (K <= 64).
+ * ------------------------------------------------------------------------ */
+#define RAI_SDE_MAX_H 512
+#define RAI_SDE_MAX_A 32
+int rai_sde_head_fwd(const float* latent, const float* mu, const float* log_std, const float* actions, int64_t B,
+                     int32_t H, int32_t A, int32_t full_std, int32_t squash, float* logp, float* entropy,
+                     float* sigma, void* stream);
+int rai_sde_head_bwd(const float* latent, const float* mu, const float* log_std, const float* actions,
+                     const float* sigma, const float* d_logp, const float* d_entropy, int64_t B, int32_t H,
+                     int32_t A, int32_t full_std, int32_t squash, float* d_mu, float* d_log_std,
+                     int32_t accumulate, void* stream);
+int rai_sde_sample_weights(const float* log_std, int64_t N, int32_t H, int32_t A, int32_t full_std, uint64_t seed,
+                           uint64_t offset, float* E, float* E0, void* stream);
+int rai_sde_sample(const float* mu, const float* latent, const float* log_std, const float* E, int64_t e_stride,
+                   int64_t N, int32_t H, int32_t A, int32_t full_std, int32_t squash, const float* low,
+                   const float* high, float* actions_out, float* clamped_out, float* logp_out, const float* v_in,
+                   float* v_out, int32_t K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ RAI_WIDE_MAX_OUT = 8
 RAI_DQN_MAX_A = 256
 RAI_DQN_HEAD_MAX_H = 512
 RAI_DQN_HEAD_MAX_A = 32
+RAI_SDE_MAX_H = 512
+RAI_SDE_MAX_A = 32
 RAI_STAT_STRIDE = 5 + 2 * RAI_MAX_K
 ABI_VERSION = 1
 # the RAI_E_* return codes of include/rai_amd.h (tests/test_boundary.py checks them against the header)
@@ -278,6 +280,11 @@ _SIGNATURES = {
     "rai_dqn_head_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "rai_argmax_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "rai_polyak_update": (C.c_int, [_vp, _vp, _i64, C.c_double, C.c_double, _vp]),
+    "rai_sde_head_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rai_sde_head_bwd": (C.c_int, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "rai_sde_sample_weights": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _vp]),
+    "rai_sde_sample": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _i32, _vp]),
 }
 RAI_DP_UID_BYTES = 128
 EXPORTED = tuple(_SIGNATURES)

@@ -464,6 +464,80 @@ class GaussianActorHead(nn.Module):
         return (self.act_dim,)
 
 
+class StateDependentNoiseActorHead(nn.Module):
+    """gSDE head (shared/actor/state_dependent_noise.py:86-186): latent_net (the hidden layers WITH their
+    output activation, Identity when there are none), mu_net (one Linear, gain 0.01) and log_std
+    (H, A) when full_std else (H, 1).  The exploration matrices are a pure function of log_std and a
+    random draw, not parameters: exploration_matrices (one per env) and exploration_mat (shared), redrawn
+    by sample_weights().  The rollout generator keeps its own device-resident pair (rollout.py); these
+    serve step() / act()."""
+
+    def __init__(self, act_dim, in_dim, hidden_sizes=(32,), activation=nn.Tanh, init_layers_orthogonal=True,
+                 log_std_init=-0.5, full_std=True, squash_output=False):
+        super().__init__()
+        self.act_dim = act_dim
+        layer_sizes = (in_dim,) + tuple(hidden_sizes) + (act_dim,)
+        if len(layer_sizes) == 2:
+            self.latent_net = nn.Identity()
+        else:
+            self.latent_net = mlp(layer_sizes[:-1], activation, output_activation=activation,
+                                  init_layers_orthogonal=init_layers_orthogonal)
+        self.mu_net = mlp(layer_sizes[-2:], activation, init_layers_orthogonal=init_layers_orthogonal,
+                          final_layer_gain=0.01)
+        self.full_std = full_std
+        self.squash_output = squash_output
+        self.latent_dim = layer_sizes[-2]
+        self.log_std = nn.Parameter(torch.ones((self.latent_dim, act_dim if full_std else 1),
+                                               dtype=torch.float32) * log_std_init)
+        self.exploration_mat: Optional[torch.Tensor] = None
+        self.exploration_matrices: Optional[torch.Tensor] = None
+        self.sample_weights()  # as the reference's constructor: the same draws from torch's generator
+
+    def std(self) -> torch.Tensor:  # _get_std
+        std = torch.exp(self.log_std)
+        if self.full_std:
+            return std
+        return torch.ones(self.latent_dim, self.act_dim, dtype=std.dtype, device=std.device) * std
+
+    @torch.no_grad()
+    def sample_weights(self, batch_size: int = 1) -> None:
+        # Normal(0, std).rsample(): eps * std with eps = empty(shape).normal_(), the shared matrix first
+        std = self.std()
+        self.exploration_mat = torch.empty_like(std).normal_() * std
+        self.exploration_matrices = torch.empty((batch_size,) + tuple(std.shape), dtype=std.dtype,
+                                                device=std.device).normal_() * std
+
+    def params(self, x):
+        """(mu, latent): what logp_entropy, sample and mode take."""
+        latent = self.latent_net(x)
+        return self.mu_net(latent), latent.detach()
+
+    def logp_entropy(self, params, actions, action_masks=None):
+        assert action_masks is None, "StateDependentNoiseActorHead does not support action_masks"
+        from .sde_ops import logp_entropy
+
+        mu, latent = params
+        return logp_entropy(mu, self.log_std, latent, actions, self.full_std, self.squash_output)
+
+    def noise(self, latent: torch.Tensor) -> torch.Tensor:  # _get_noise
+        if len(latent) == 1 or len(latent) != len(self.exploration_matrices):
+            return torch.mm(latent, self.exploration_mat)
+        return torch.bmm(latent.unsqueeze(1), self.exploration_matrices).squeeze(1)
+
+    def sample(self, params) -> torch.Tensor:
+        mu, latent = params
+        a = mu + self.noise(latent)
+        return torch.tanh(a) if self.squash_output else a
+
+    def mode(self, params, action_masks=None):
+        mu = params[0]
+        return torch.tanh(mu) if self.squash_output else mu
+
+    @property
+    def action_shape(self):
+        return (self.act_dim,)
+
+
 class CriticHead(nn.Module):
     def __init__(self, in_dim, hidden_sizes=(), activation=nn.Tanh, init_layers_orthogonal=True):
         super().__init__()
@@ -478,7 +552,7 @@ class ConnectedTrioNetwork(nn.Module):
     def __init__(self, observation_space, action_space, pi_hidden_sizes=None, v_hidden_sizes=None,
                  init_layers_orthogonal=True, activation_fn="tanh", log_std_init=-0.5,
                  cnn_flatten_dim=512, cnn_style="nature", cnn_layers_init_orthogonal=None,
-                 impala_channels=(16, 32, 32)):
+                 impala_channels=(16, 32, 32), use_sde=False, full_std=True, squash_output=False):
         super().__init__()
         pi_hidden_sizes = pi_hidden_sizes if pi_hidden_sizes is not None else default_hidden_sizes(observation_space)
         v_hidden_sizes = v_hidden_sizes if v_hidden_sizes is not None else default_hidden_sizes(observation_space)
@@ -490,6 +564,9 @@ class ConnectedTrioNetwork(nn.Module):
         if is_discrete(action_space):
             self._pi = CategoricalActorHead(action_space.n, in_dim, tuple(pi_hidden_sizes), activation,
                                             init_layers_orthogonal)
+        elif is_box(action_space) and use_sde:  # make_actor.py: the gSDE head for Box spaces
+            self._pi = StateDependentNoiseActorHead(action_space.shape[0], in_dim, tuple(pi_hidden_sizes), activation,
+                                                    init_layers_orthogonal, log_std_init, full_std, squash_output)
         elif is_box(action_space):
             self._pi = GaussianActorHead(action_space.shape[0], in_dim, tuple(pi_hidden_sizes), activation,
                                          init_layers_orthogonal, log_std_init)
@@ -526,8 +603,18 @@ class ConnectedTrioNetwork(nn.Module):
         enc = self._feature_extractor(obs)
         return self._pi.params(enc), self._v(enc)
 
+    def sde_params_and_value(self, obs):
+        """(mu, latent, v) of a gSDE policy: the rollout's graph-replayed forward (rai_sde_sample's inputs)."""
+        enc = self._feature_extractor(obs)
+        mu, latent = self._pi.params(enc)
+        return mu, latent, self._v(enc)
+
     def value(self, obs):
         return self._v(self._feature_extractor(obs))
+
+    def reset_noise(self, batch_size: int = 1) -> None:
+        if isinstance(self._pi, StateDependentNoiseActorHead):
+            self._pi.sample_weights(batch_size=batch_size)
 
 
 class ActorCritic(nn.Module):
@@ -545,8 +632,7 @@ class ActorCritic(nn.Module):
                  save_critic_separate=None, shared_critic_head=None, normalization=None,
                  impala_channels=(16, 32, 32), **kwargs):
         super().__init__()
-        if use_sde or squash_output:
-            raise NotImplementedError("gSDE / squash_output are outside the hot-path scope")
+        assert use_sde or not squash_output, "squash_output only valid if use_sde"  # shared/actor/make_actor.py
         if not share_features_extractor:
             raise NotImplementedError("SeparateActorCriticNetwork is outside the hot-path scope")
         if actor_head_style not in ("single", "squeeze_unet"):
@@ -554,8 +640,11 @@ class ActorCritic(nn.Module):
         self.env = env
         self.action_space = env.single_action_space
         self.observation_space = env.single_observation_space
+        assert not use_sde or is_box(env.single_action_space), "use_sde only valid if Box action_space"
         self.squash_output = squash_output
         self.gridnet = actor_head_style == "squeeze_unet"
+        if self.gridnet and use_sde:
+            raise NotImplementedError("use_sde with actor_head_style=squeeze_unet is outside the hot-path scope")
         if self.gridnet:  # actor_critic.py:200-229 (MicroRTS, config C5)
             from .backbone import SqueezeUnetActorCriticNetwork
 
@@ -580,7 +669,8 @@ class ActorCritic(nn.Module):
             self.network = ConnectedTrioNetwork(env.single_observation_space, env.single_action_space,
                                                 pi_hidden_sizes, v_hidden_sizes, init_layers_orthogonal,
                                                 activation_fn, log_std_init, cnn_flatten_dim, cnn_style,
-                                                cnn_layers_init_orthogonal, tuple(impala_channels))
+                                                cnn_layers_init_orthogonal, tuple(impala_channels),
+                                                use_sde=use_sde, full_std=full_std, squash_output=squash_output)
         self._device: Optional[torch.device] = None
         # policy.py:31-36: the env's normalisation statistics travel with the checkpoint
         from .wrappers import NormalizeObservation, NormalizeReward, find_wrapper
@@ -596,6 +686,10 @@ class ActorCritic(nn.Module):
         super().to(device, *args, **kwargs)
         if device is not None:
             self._device = torch.device(device)
+            if self.use_sde:  # the exploration matrices are plain tensors (not in the state_dict): they follow
+                pi = self.network._pi
+                pi.exploration_mat = pi.exploration_mat.to(self._device)
+                pi.exploration_matrices = pi.exploration_matrices.to(self._device)
         return self
 
     @property
@@ -614,6 +708,10 @@ class ActorCritic(nn.Module):
     @property
     def is_discrete(self) -> bool:
         return not self.gridnet and isinstance(self.network._pi, CategoricalActorHead)
+
+    @property
+    def use_sde(self) -> bool:
+        return not self.gridnet and isinstance(self.network._pi, StateDependentNoiseActorHead)
 
     def forward(self, obs, action, action_masks=None, obs_prepared: bool = False) -> ACForward:
         """obs_prepared: obs came through the minibatch gather's transform (obs_transform())"""
@@ -660,11 +758,15 @@ class ActorCritic(nn.Module):
                     params = torch.where(m, params, F32_MIN)
                 a = torch.multinomial(torch.softmax(params, -1), 1).squeeze(-1)
                 logp, _ = self.network._pi.logp_entropy(params, a, m)
+            elif self.use_sde:  # per-env matrices when the batch matches them, else the shared one
+                a = self.network._pi.sample(params)
+                logp, _ = self.network._pi.logp_entropy(params, a)
             else:
                 a = params + torch.exp(self.network._pi.log_std) * torch.randn_like(params)
                 logp, _ = self.network._pi.logp_entropy(params, a)
         a_np = a.cpu().numpy()
-        return Step(a_np, v.cpu().numpy(), logp.cpu().numpy(), clamp_actions(a_np, self.action_space, False))
+        return Step(a_np, v.cpu().numpy(), logp.cpu().numpy(),
+                    clamp_actions(a_np, self.action_space, self.squash_output))
 
     def act(self, obs: np.ndarray, deterministic: bool = True, action_masks=None) -> np.ndarray:
         if not deterministic:
@@ -680,7 +782,12 @@ class ActorCritic(nn.Module):
         return clamp_actions(a.cpu().numpy(), self.action_space, self.squash_output)
 
     def reset_noise(self, batch_size: Optional[int] = None) -> None:
-        pass
+        """actor_critic.py:371-374: redraw the gSDE exploration matrices (one per env by default); nothing to
+        do for the other heads.  Noise does not enter log_prob, so the trainers' per-optimizer-step call of
+        the reference has no counterpart here."""
+        network = getattr(self, "network", None)  # (DQNPolicy borrows this method: no actor network)
+        if isinstance(network, ConnectedTrioNetwork):
+            network.reset_noise(batch_size=batch_size if batch_size else self.env.num_envs)
 
     def save_weights(self, path: str) -> None:
         torch.save(self.state_dict(), os.path.join(path, MODEL_FILENAME))
@@ -706,6 +813,19 @@ class ActorCritic(nn.Module):
         if self.norm_reward_rms:
             self.norm_reward_rms.load(os.path.join(path, NORMALIZE_REWARD_FILENAME),
                                       count_override=load_norm_rms_count_override)
+        self.reset_noise()  # actor_critic.py:360-364
+
+    def load_from(self, policy: "ActorCritic") -> "ActorCritic":  # policy.py:103-112, actor_critic.py:366-369
+        self.load_state_dict(policy.state_dict())
+        if self.norm_observation_rms:
+            assert policy.norm_observation_rms
+            self.norm_observation_rms.load_from(policy.norm_observation_rms)
+        if self.norm_reward_rms:
+            assert policy.norm_reward_rms
+            assert type(self.norm_reward_rms) == type(policy.norm_reward_rms)
+            self.norm_reward_rms.load_from(policy.norm_reward_rms)
+        self.reset_noise()
+        return self
 
     def sync_normalization(self, destination_env) -> None:  # policy.py:141-152
         from copy import deepcopy

@@ -317,7 +317,7 @@ class DeviceRollout(Rollout):
         raise NotImplementedError("teacher-KL additional batch fields are outside the hot-path scope")
 
 
-_UNSUPPORTED_GEN_KW = ("sde_sample_freq", "num_envs_reset_every_rollout", "rolling_num_envs_reset_every_rollout",
+_UNSUPPORTED_GEN_KW = ("num_envs_reset_every_rollout", "rolling_num_envs_reset_every_rollout",
                        "random_num_envs_reset_every_rollout", "prepare_steps",
                        "rolling_num_envs_reset_every_prepare_step")
 
@@ -332,8 +332,7 @@ class SyncStepRolloutGenerator(RolloutGenerator):
                  prepare_steps: int = 0, rolling_num_envs_reset_every_prepare_step: int = 0,
                  gae_mode: int = EXACT, seed: Optional[int] = None) -> None:
         super().__init__(policy, vec_env)
-        bad = [k for k, v, d in [("sde_sample_freq", sde_sample_freq, -1),
-                                 ("num_envs_reset_every_rollout", num_envs_reset_every_rollout, 0),
+        bad = [k for k, v, d in [("num_envs_reset_every_rollout", num_envs_reset_every_rollout, 0),
                                  ("rolling_num_envs_reset_every_rollout", rolling_num_envs_reset_every_rollout, 0),
                                  ("random_num_envs_reset_every_rollout", random_num_envs_reset_every_rollout, 0),
                                  ("prepare_steps", prepare_steps, 0),
@@ -423,9 +422,56 @@ class SyncStepRolloutGenerator(RolloutGenerator):
 
             if wide_mlp_spec(policy) is not None and N <= _lib.RAI_WIDE_MAX_B:
                 self._wide_fwd = WideRolloutForward(policy, dev, N)
+        # gSDE policies: the generator owns the exploration matrices, one per env (E) and the shared one (E0),
+        # redrawn on the device at the reference's reset points (rai_sde_sample_weights, outside the captured
+        # forward graph); for the other heads sde_sample_freq is accepted and ignored, as in the reference
+        self.sde_sample_freq = sde_sample_freq
+        self.sde = None
+        if getattr(policy, "use_sde", False):
+            from .sde_ops import in_limits
+
+            self.sde = policy.network._pi
+            H, A = self.sde.latent_dim, self.sde.act_dim
+            self._sde_kernels = self.device.type == "cuda" and in_limits(H, A)
+            if self._sde_kernels:
+                self.sde_E = torch.zeros((N, H, A), dtype=torch.float32, device=dev)
+                self.sde_E0 = torch.zeros((H, A), dtype=torch.float32, device=dev)
         obs, _ = vec_env.reset()
         self._stage_obs(obs)
         self._stage_masks()
+
+    def _sde_reset_noise(self) -> None:
+        """policy.reset_noise() of the rollout loop (sync_step_rollout.py:183-186): new exploration matrices,
+        one launch, one rng_offset."""
+        if not self._sde_kernels:  # outside the kernels' limits: the head's own torch matrices
+            self.policy.reset_noise(self.num_envs)
+            return
+        from .sde_ops import sample_weights
+
+        sample_weights(self.sde.log_std, self.sde_E, self.sde_E0, self.sde.full_std, self.seed, self.rng_offset)
+        self.rng_offset += 1
+
+    def _sde_sample(self, mu: torch.Tensor, latent: torch.Tensor, v: torch.Tensor, s: int) -> None:
+        """Action, clamped action, log-prob and value of env step s into the slot (rai_sde_sample); the
+        per-env matrices, as the batch is the env group (state_dependent_noise.py:64-73)."""
+        pi = self.sde
+        mu, latent, v = mu.contiguous().float(), latent.contiguous().float(), v.contiguous().float()
+        if self._sde_kernels:
+            from .sde_ops import sample
+
+            per_env = self.num_envs > 1  # a batch of one takes the shared matrix (_get_noise)
+            sample(mu, latent, pi.log_std, self.sde_E if per_env else self.sde_E0, per_env, pi.full_std,
+                   pi.squash_output, self.act_low, self.act_high, self.actions[s], self.clamped, self.logprobs[s],
+                   v, self.values[s], 1)
+            return
+        a = pi.sample((mu, latent))
+        self.actions[s].copy_(a)
+        self.logprobs[s].copy_(pi.logp_entropy((mu, latent), a)[0])
+        self.values[s].copy_(v)
+        if pi.squash_output:
+            self.clamped.copy_(self.act_low + 0.5 * (a + 1) * (self.act_high - self.act_low))
+        else:
+            self.clamped.copy_(torch.minimum(torch.maximum(a, self.act_low), self.act_high))
 
     def _stage_masks(self) -> None:
         if self.action_masks is not None:
@@ -554,6 +600,8 @@ class SyncStepRolloutGenerator(RolloutGenerator):
                 self._fused_step_loop()
             return self._finish_rollout(output_next_values)
         for s in range(self.n_steps):
+            if self.sde is not None and (s == 0 or (self.sde_sample_freq > 0 and s % self.sde_sample_freq == 0)):
+                self._sde_reset_noise()
             if not direct or s == 0:
                 self.obs[s].copy_(self.next_obs_dev)
                 self.episode_starts[s].copy_(self.next_episode_starts)
@@ -563,6 +611,8 @@ class SyncStepRolloutGenerator(RolloutGenerator):
                 self._fused_step(s)
             elif self.gridnet:
                 self._gridnet_step(s)
+            elif self.sde is not None:
+                self._sde_sample(*self._policy_forward(net.sde_params_and_value), s)
             else:
                 params, v = self._policy_forward(self._wide_fwd if self._wide_fwd is not None
                                                  else net.dist_params_and_value)
