@@ -955,6 +955,46 @@ int rai_sde_sample(const float* mu, const float* latent, const float* log_std, c
                    const float* high, float* actions_out, float* clamped_out, float* logp_out, const float* v_in,
                    float* v_out, int32_t K, void* stream);
 
+/* --------------------------------------------------------------------------
+ * MultiDiscrete actor head and flat action masks (csrc/multidiscrete.hip, csrc/md_row.h).  Replaces
+ * rl_algo_impls/shared/actor/multi_discrete.py:15-105 (MultiCategorical and the head's final Linear) over
+ * rl_algo_impls/shared/actor/categorical.py:12-54 (MaskedCategorical).
+ * nvec (G) is a HOST array read at call time; A = sum(nvec); group g is logits [off_g, off_g + nvec[g]).
+ * x (B, H): the input of the head's final Linear; W (A, H), b (A); mask (B, A) uint8 or NULL (all valid);
+ * actions (B, G) int64, each in [0, nvec[g]) (outside: that row's logp is NaN, nothing is read past a group).
+ *   z = x W^T + b                      (double accumulation, rounded once; `logits`, which the backward reads)
+ *   zm = mask ? z : finfo(float32).min,  n_g = zm_g - logsumexp(zm_g) per group
+ *   logp[b]    = sum_g n_g[action_g]
+ *   entropy[b] = sum_g -sum_{valid a} p log p          (masked and plain form agree: a masked p is 0)
+ * A group whose mask is all false contributes log-prob 0, entropy 0 and no gradient: the reference's float32
+ * result there (finfo.min + log n rounds back to finfo.min, so its normalised logits are 0).
+ * Supported: 1 <= H <= RAI_MD_MAX_H, A <= RAI_GRID_MAX_A, G <= RAI_MD_MAX_G (else RAI_E_UNSUPPORTED: the caller
+ * takes torch for the Linear and rai_gridnet_logp_entropy with one cell, or the torch formula); a malformed
+ * nvec is RAI_E_SHAPE.
+ *
+ * rai_md_head_fwd: one launch.  actions == NULL: the logits alone (logp / entropy may be NULL): the rollout's
+ * forward, so that the sampler and the update see the same logit bits.
+ * rai_md_head_bwd, from d_logp (B) and d_entropy (B): two launches.  dx (B, H); dW (A, H) and db (A) summed
+ * over the batch in ascending b (no atomics: two calls give the same bits), written (accumulate == 0) or added
+ * (accumulate != 0: the flat .grad views).  d_logits (B, A) is scratch the second launch reads.
+ * rai_md_sample, per row n of logits (N, A): action g by inverse CDF over the VALID entries of group g
+ * (Philox4x32-10, key seed, counter (offset, 8 n + g / 4), word g % 4; an all-false group: uniform over its
+ * entries), logp_out of the stored actions by the same device functions as rai_md_head_fwd (bit-identical
+ * for equal logits and mask), v_out (N, K) = v_in when both are given (K <= 64).  One launch.
+ * ------------------------------------------------------------------------ */
+#define RAI_MD_MAX_H 512
+#define RAI_MD_MAX_G 32
+int rai_md_head_fwd(const float* x, const float* W, const float* b, const uint8_t* mask, const int64_t* actions,
+                    const int32_t* nvec, int32_t G, int64_t B, int32_t H, float* logits, float* logp,
+                    float* entropy, void* stream);
+int rai_md_head_bwd(const float* x, const float* W, const float* logits, const uint8_t* mask,
+                    const int64_t* actions, const int32_t* nvec, int32_t G, const float* d_logp,
+                    const float* d_entropy, int64_t B, int32_t H, float* d_logits, float* dx, float* dW, float* db,
+                    int32_t accumulate, void* stream);
+int rai_md_sample(const float* logits, const uint8_t* mask, const int32_t* nvec, int32_t G, int64_t N,
+                  uint64_t seed, uint64_t offset, int64_t* actions_out, float* logp_out, const float* v_in,
+                  float* v_out, int32_t K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,8 @@ RAI_DQN_HEAD_MAX_H = 512
 RAI_DQN_HEAD_MAX_A = 32
 RAI_SDE_MAX_H = 512
 RAI_SDE_MAX_A = 32
+RAI_MD_MAX_H = 512
+RAI_MD_MAX_G = 32
 RAI_STAT_STRIDE = 5 + 2 * RAI_MAX_K
 ABI_VERSION = 1
 # the RAI_E_* return codes of include/rai_amd.h (tests/test_boundary.py checks them against the header)
@@ -285,6 +287,9 @@ _SIGNATURES = {
     "rai_sde_sample_weights": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _vp]),
     "rai_sde_sample": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _i32, _vp]),
+    "rai_md_head_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "rai_md_head_bwd": (C.c_int, [_vp] * 6 + [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "rai_md_sample": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _u64, _u64, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 RAI_DP_UID_BYTES = 128
 EXPORTED = tuple(_SIGNATURES)

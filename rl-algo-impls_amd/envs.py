@@ -168,6 +168,67 @@ class SyntheticVecEnv:
         pass
 
 
+class MaskedMultiDiscreteVecEnv:
+    """Seeded synthetic vector env with a flat MultiDiscrete(nvec) action space and get_action_mask():
+    obs ~ N(0, 1) f32 (N, obs_dim), fresh every step; the (N, sum(nvec)) bool mask is a pure function of the
+    current observation (mask_of), so a mask that lags its observation by a step shows; every group keeps at
+    least one valid entry.  Reward: the fraction of a row's sub-actions that are valid under the mask the
+    env handed out (1.0 for a policy that respects it); invalid_actions counts the others.  Termination
+    ~ Bernoulli(term_prob)."""
+
+    def __init__(self, num_envs: int, nvec=(3, 5, 2), obs_dim: int = 5, seed: int = 1, term_prob: float = 1 / 50):
+        self.num_envs = int(num_envs)
+        self.rng = np.random.default_rng(seed)
+        self.single_observation_space = Box(-np.inf, np.inf, (obs_dim,), np.float32)
+        self.single_action_space = MultiDiscrete(nvec)
+        self.nvec = self.single_action_space.nvec
+        self.term_prob = term_prob
+        self.invalid_actions = 0
+        self._obs = self._draw()
+
+    @property
+    def unwrapped(self):
+        return self
+
+    def _draw(self) -> np.ndarray:
+        return self.rng.standard_normal((self.num_envs,) + self.single_observation_space.shape, dtype=np.float32)
+
+    def mask_of(self, obs: np.ndarray) -> np.ndarray:
+        """Entry a of a row is valid when obs[a % obs_dim] * (-1)^a > -0.4 (about two in three); entry
+        floor(8 |obs[g % obs_dim]|) % nvec[g] of group g is always valid."""
+        nvec = self.nvec
+        obs = np.asarray(obs, dtype=np.float32)
+        A, D = int(nvec.sum()), obs.shape[1]
+        a = np.arange(A)
+        mask = obs[:, a % D] * np.where(a % 2 == 0, 1.0, -1.0).astype(np.float32) > np.float32(-0.4)
+        off = np.concatenate([[0], np.cumsum(nvec)])
+        for g, n in enumerate(nvec):
+            keep = np.floor(8.0 * np.abs(obs[:, g % D])).astype(np.int64) % int(n)
+            mask[np.arange(obs.shape[0]), off[g] + keep] = True
+        return mask
+
+    def get_action_mask(self) -> np.ndarray:
+        return self.mask_of(self._obs)
+
+    def reset(self, **kwargs) -> Tuple[np.ndarray, Dict[str, Any]]:
+        self._obs = self._draw()
+        return self._obs, {}
+
+    def step(self, actions):
+        nvec = self.nvec
+        a = np.asarray(actions).reshape(self.num_envs, len(nvec))
+        off = np.concatenate([[0], np.cumsum(nvec)])[:-1]
+        in_range = (a >= 0) & (a < nvec)
+        valid = in_range & np.take_along_axis(self.get_action_mask(), off + np.where(in_range, a, 0), axis=1)
+        self.invalid_actions += int((~valid).sum())
+        self._obs = self._draw()
+        term = self.rng.random(self.num_envs) < self.term_prob
+        return self._obs, valid.mean(axis=1).astype(np.float32), term, np.zeros(self.num_envs, dtype=np.bool_), {}
+
+    def close(self):
+        pass
+
+
 class CartPoleVecEnv:
     """Vectorised CartPole-v1 (gymnasium 0.29 public dynamics: Euler integration,
     tau=0.02, force 10, pole half-length 0.5, termination |x|>2.4 or

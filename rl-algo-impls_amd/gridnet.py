@@ -63,6 +63,15 @@ def categorical_spec(n: int) -> "_Spec":
     return sp
 
 
+def multidiscrete_spec(nvec) -> "_Spec":
+    """A flat MultiDiscrete(nvec) as a GridNet head with one cell."""
+    key = tuple(int(n) for n in nvec)
+    sp = _CAT_SPECS.get(key)
+    if sp is None:
+        sp = _CAT_SPECS[key] = _Spec(list(key), None)
+    return sp
+
+
 def _u8(m: torch.Tensor) -> torch.Tensor:
     m = m.contiguous()
     return m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)

@@ -11,6 +11,7 @@ rl_algo_impls/shared/policy/actor_critic_network/connected_trio.py:17-116):
                                ImpalaCnn with cnn_style="impala" (shared/encoder/impala_cnn.py)
   network._pi                  CategoricalActorHead._fc (shared/actor/categorical.py:57-87)
                                or GaussianActorHead.{log_std, mu_net} (shared/actor/gaussian.py:19-61)
+                               or MultiDiscreteActorHead._fc (shared/actor/multi_discrete.py:69-105)
   network._v                   CriticHead._fc = Sequential(mlp) (shared/policy/critic.py:11-41)
 
 Modules are constructed (and layer_init'ed, shared/module/utils.py:7-45) in the
@@ -32,7 +33,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .envs import is_box, is_discrete
+from .envs import is_box, is_discrete, is_multidiscrete
 
 ACTIVATION = {"tanh": nn.Tanh, "relu": nn.ReLU, "identity": nn.Identity, "sigmoid": nn.Sigmoid}
 MODEL_FILENAME = "model.pth"
@@ -538,6 +539,78 @@ class StateDependentNoiseActorHead(nn.Module):
         return (self.act_dim,)
 
 
+class MultiDiscreteActorHead(nn.Module):
+    """MultiDiscrete head (shared/actor/multi_discrete.py:69-105): _fc ends in sum(nvec) logits, split into
+    len(nvec) groups, each a MaskedCategorical (shared/actor/categorical.py:12-54) under MultiCategorical.
+    params() is the INPUT of the final Linear: on the GPU that Linear, the masked per-group log-softmax, the
+    log-prob and the entropy are one launch (md_ops.MdHeadLogpEntropy over csrc/multidiscrete.hip); logits()
+    is the same kernel's Linear alone, which sample / mode / the rollout use."""
+
+    def __init__(self, nvec, in_dim, hidden_sizes=(32,), activation=nn.ReLU, init_layers_orthogonal=True):
+        super().__init__()
+        self.nvec = np.asarray(nvec, dtype=np.int64)
+        assert self.nvec.ndim == 1 and len(self.nvec) >= 1 and (self.nvec >= 1).all(), f"nvec {nvec}"
+        self._sizes = tuple(int(n) for n in self.nvec)
+        self.act_dim = int(self.nvec.sum())
+        self._fc = mlp((in_dim,) + tuple(hidden_sizes) + (self.act_dim,), activation,
+                       init_layers_orthogonal=init_layers_orthogonal, final_layer_gain=0.01)
+
+    @property
+    def final(self) -> nn.Linear:
+        return self._fc[-2]  # mlp(): ..., Linear, output_activation()
+
+    def params(self, x):
+        """The final Linear's input (the hidden layers with their activations; x itself when there are none)."""
+        for layer in list(self._fc)[:-2]:
+            x = layer(x)
+        return x
+
+    def logits(self, hidden):
+        from . import md_ops
+
+        if not torch.is_grad_enabled() and md_ops.fusable(hidden, self.final, self._sizes):
+            return md_ops.logits(hidden, self.final, self._sizes)
+        return self.final(hidden)
+
+    def logp_entropy(self, hidden, actions, action_masks=None):
+        """MultiCategorical.log_prob / entropy of the rows.  On the GPU within the kernels' limits: the fused
+        head; beyond them (or for a non-contiguous input) torch's Linear, then the GridNet operator with one
+        cell where it fits (G <= 8, A <= 256), else the plain torch formula; on the CPU plain torch."""
+        from . import _lib, md_ops
+
+        if md_ops.fusable(hidden, self.final, self._sizes):
+            return md_ops.MdHeadLogpEntropy.apply(hidden, self.final.weight, self.final.bias, actions, action_masks,
+                                                  self._sizes)
+        logits = self.final(hidden)
+        B, A, G = int(logits.shape[0]), self.act_dim, len(self._sizes)
+        if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and A <= _lib.RAI_GRID_MAX_A
+                and G <= _lib.RAI_GRID_MAX_G):
+            from .gridnet import GridnetLogpEntropy, multidiscrete_spec
+
+            masks = (action_masks.reshape(B, 1, A) if action_masks is not None
+                     else torch.ones((B, 1, A), dtype=torch.bool, device=logits.device))
+            return GridnetLogpEntropy.apply(logits.reshape(B, 1, A), masks, actions.long().reshape(B, 1, G),
+                                            multidiscrete_spec(self._sizes))
+        return md_ops.logp_entropy_torch(logits, self._sizes, actions, action_masks)
+
+    def _masked_groups(self, logits, action_masks):
+        if action_masks is not None:
+            logits = torch.where(action_masks, logits, torch.finfo(logits.dtype).min)
+        return torch.split(logits, self._sizes, dim=-1)
+
+    def sample(self, hidden, action_masks=None) -> torch.Tensor:
+        """MultiCategorical.sample: one multinomial draw per group from the masked, normalised logits."""
+        groups = self._masked_groups(self.logits(hidden), action_masks)
+        return torch.stack([torch.multinomial(torch.softmax(g, -1), 1).squeeze(-1) for g in groups], dim=-1)
+
+    def mode(self, hidden, action_masks=None):
+        return torch.stack([g.argmax(-1) for g in self._masked_groups(self.logits(hidden), action_masks)], dim=-1)
+
+    @property
+    def action_shape(self):
+        return (len(self._sizes),)
+
+
 class CriticHead(nn.Module):
     def __init__(self, in_dim, hidden_sizes=(), activation=nn.Tanh, init_layers_orthogonal=True):
         super().__init__()
@@ -570,6 +643,9 @@ class ConnectedTrioNetwork(nn.Module):
         elif is_box(action_space):
             self._pi = GaussianActorHead(action_space.shape[0], in_dim, tuple(pi_hidden_sizes), activation,
                                          init_layers_orthogonal, log_std_init)
+        elif is_multidiscrete(action_space):  # make_actor.py: actor_head_style "single"
+            self._pi = MultiDiscreteActorHead(action_space.nvec, in_dim, tuple(pi_hidden_sizes), activation,
+                                              init_layers_orthogonal)
         else:
             raise NotImplementedError(f"action space {action_space} is outside the hot-path scope")
         self._v = CriticHead(in_dim, v_hidden_sizes, activation, init_layers_orthogonal)
@@ -608,6 +684,12 @@ class ConnectedTrioNetwork(nn.Module):
         enc = self._feature_extractor(obs)
         mu, latent = self._pi.params(enc)
         return mu, latent, self._v(enc)
+
+    def md_logits_and_value(self, obs):
+        """(logits, v) of a MultiDiscrete policy: the rollout's graph-replayed forward (rai_md_sample's inputs),
+        the logits by the head kernel's own Linear so that the update recomputes the same bits."""
+        enc = self._feature_extractor(obs)
+        return self._pi.logits(self._pi.params(enc)), self._v(enc)
 
     def value(self, obs):
         return self._v(self._feature_extractor(obs))
@@ -710,6 +792,10 @@ class ActorCritic(nn.Module):
         return not self.gridnet and isinstance(self.network._pi, CategoricalActorHead)
 
     @property
+    def is_multidiscrete(self) -> bool:
+        return not self.gridnet and isinstance(self.network._pi, MultiDiscreteActorHead)
+
+    @property
     def use_sde(self) -> bool:
         return not self.gridnet and isinstance(self.network._pi, StateDependentNoiseActorHead)
 
@@ -757,6 +843,10 @@ class ActorCritic(nn.Module):
                 if m is not None:
                     params = torch.where(m, params, F32_MIN)
                 a = torch.multinomial(torch.softmax(params, -1), 1).squeeze(-1)
+                logp, _ = self.network._pi.logp_entropy(params, a, m)
+            elif self.is_multidiscrete:
+                m = self._as_tensor(action_masks) if action_masks is not None else None
+                a = self.network._pi.sample(params, m)
                 logp, _ = self.network._pi.logp_entropy(params, a, m)
             elif self.use_sde:  # per-env matrices when the batch matches them, else the shared one
                 a = self.network._pi.sample(params)

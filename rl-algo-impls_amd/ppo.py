@@ -673,6 +673,8 @@ class PPO:
         RAI_WIDE_EPOCH=0 keeps the graph-replayed per-minibatch path."""
         if not hasattr(r, "epoch_batch") or (self.dp_enabled and self._xdp is None):
             return None
+        if getattr(r, "action_masks", None) is not None:  # the kernel has no mask input
+            return None
         if not self._wide_epoch_options_ok():
             return None
         if r.total_steps < 2 or (not self.dp_enabled and r.total_steps % self.batch_size == 1):
@@ -875,7 +877,10 @@ class PPO:
             if self.world > 1 and not self._params_agree():
                 raise RuntimeError("ranks' parameters diverged under the replicated data-parallel update")
             return out
-        spec = self.fused_mlp_spec() if hasattr(r, "epoch_batch") else None
+        # the whole-epoch kernels (CartPole-class and wide MLP) take no action masks: a masked rollout runs
+        # the per-minibatch path below, whose policy forward receives Batch.action_masks
+        masked = getattr(r, "action_masks", None) is not None
+        spec = self.fused_mlp_spec() if hasattr(r, "epoch_batch") and not masked else None
         if spec is not None:
             return self._update_fused_dp(r, spec) if self.dp_enabled else self._update_fused(r, spec)
         wide_epoch = self._wide_epoch_step(r)

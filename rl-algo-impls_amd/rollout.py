@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .envs import is_box, is_discrete
+from .envs import is_box, is_discrete, is_multidiscrete
 from .gae import EXACT, compute_advantages_device
 
 
@@ -183,7 +183,10 @@ class DeviceRollout(Rollout):
         self.action_masks = action_masks
         self.next_episode_starts, self.next_values = next_episode_starts, next_values
         self.num_actions = None
-        if action_masks is not None:  # vec_rollout.py:69-76 -> rollout.py:130-180, one launch
+        # vec_rollout.py:69-76 -> rollout.py:130-180, one launch.  Flat (T, N, A) masks of a Discrete or
+        # MultiDiscrete policy carry no num_actions: the reference's per_position_num_actions sums such a
+        # mask over the env axis into a (T,) array its own Batch.__getitem__ cannot index
+        if action_masks is not None and (isinstance(action_masks, dict) or action_masks.dim() >= 4):
             self.num_actions = _num_actions(actions, action_masks, subaction_mask, action_plane_space)
         self.advantages, self.returns = compute_advantages_device(
             rewards, values, episode_starts, next_episode_starts, next_values, gamma, gae_lambda,
@@ -346,8 +349,6 @@ class SyncStepRolloutGenerator(RolloutGenerator):
         self.action_plane_space = getattr(vec_env, "action_plane_space", None)
         self.gridnet = bool(getattr(policy, "gridnet", False))
         self.get_action_mask = getattr(vec_env, "get_action_mask", None)
-        if self.get_action_mask is not None and not self.gridnet:
-            raise NotImplementedError("action masks are on the hot path for GridNet (squeeze_unet) policies only")
         if self.gridnet and self.get_action_mask is None:
             raise AssertionError("GridNet policies need the env's get_action_mask()")
         self.n_steps = n_steps
@@ -368,12 +369,18 @@ class SyncStepRolloutGenerator(RolloutGenerator):
         tdt = lambda d: torch.from_numpy(np.zeros((), dtype=d)).dtype
         self.obs_dtype = tdt(obs_space.dtype)
         self.discrete = is_discrete(act_space)
-        if not (self.discrete or is_box(act_space) or self.gridnet):
+        # a flat MultiDiscrete space (policy.MultiDiscreteActorHead): (N, G) int64 actions, rai_md_sample
+        self.multidiscrete = not self.gridnet and is_multidiscrete(act_space)
+        if not (self.discrete or self.multidiscrete or is_box(act_space) or self.gridnet):
             raise NotImplementedError(f"action space {act_space} is outside the hot-path scope")
+        if self.get_action_mask is not None and not (self.gridnet or self.discrete or self.multidiscrete):
+            raise NotImplementedError("action masks are on the hot path for Discrete, MultiDiscrete and GridNet "
+                                      "(squeeze_unet) policies only")
         # GridNet (MicroRTS): per-position actions (map cells, planes) i64, K critic columns
-        self.act_shape = tuple(policy.action_shape) if self.gridnet else (() if self.discrete else
-                                                                          tuple(act_space.shape))
-        act_dtype = torch.int64 if (self.discrete or self.gridnet) else torch.float32
+        self.act_shape = (tuple(policy.action_shape) if (self.gridnet or self.multidiscrete)
+                          else (() if self.discrete else tuple(act_space.shape)))
+        int_actions = self.discrete or self.gridnet or self.multidiscrete
+        act_dtype = torch.int64 if int_actions else torch.float32
         vshape = tuple(policy.value_shape)
         self.obs = torch.zeros((T, N) + tuple(obs_space.shape), dtype=self.obs_dtype, device=dev)
         self.rewards = torch.zeros((T, N) + vshape, dtype=torch.float32, device=dev)
@@ -382,15 +389,20 @@ class SyncStepRolloutGenerator(RolloutGenerator):
         self.action_masks = None
         self.rollout_graph = os.environ.get("RAI_ROLLOUT_GRAPH", "1") == "1" and self.device.type == "cuda"
         self._fwd_graph = None
-        if self.gridnet:  # sync_step_rollout.py:119-131: (T, N, cells, sum(nvec)) bool
+        # sync_step_rollout.py:119-131: (T, N, cells, sum(nvec)) bool (GridNet), or flat (T, N, A) masks of a
+        # Discrete / MultiDiscrete env, staged the same way
+        if self.get_action_mask is not None:
             m0 = np.asarray(self.get_action_mask())
+            if not self.gridnet:
+                A = act_space.n if self.discrete else int(np.sum(act_space.nvec))
+                assert m0.shape == (N, A) and m0.dtype == np.bool_, f"flat action mask {m0.shape} {m0.dtype}"
             self.action_masks = torch.zeros((T,) + m0.shape, dtype=torch.bool, device=dev)
             self.h_mask = torch.zeros(m0.shape, dtype=torch.bool).pin_memory()
             self.next_masks_dev = torch.zeros(m0.shape, dtype=torch.bool, device=dev)
         self.logprobs = torch.zeros((T, N), dtype=torch.float32, device=dev)
         self.actions = torch.zeros((T, N) + self.act_shape, dtype=act_dtype, device=dev)
         self.clamped = torch.zeros((N,) + self.act_shape, dtype=act_dtype, device=dev)
-        if not (self.discrete or self.gridnet):
+        if not int_actions:
             self.act_low = torch.as_tensor(np.asarray(act_space.low, np.float32), device=dev)
             self.act_high = torch.as_tensor(np.asarray(act_space.high, np.float32), device=dev)
         # pinned host staging (H2D obs/rewards/dones, D2H actions)
@@ -411,7 +423,9 @@ class SyncStepRolloutGenerator(RolloutGenerator):
 
         self.fused_step = None
         spec = mlp_actor_critic_spec(policy)
-        if spec is not None and self.discrete and self.obs_dtype == torch.float32 and len(obs_space.shape) == 1:
+        # (the fused step kernel has no mask input: a masked env takes the forward + sample launches below)
+        if (spec is not None and self.discrete and self.get_action_mask is None
+                and self.obs_dtype == torch.float32 and len(obs_space.shape) == 1):
             self.fused_step = spec
         # wide-MLP policies (HalfCheetah class): the rollout forward as rai_mlp_wide_dist_params (3
         # launches) instead of the PyTorch module; RAI_ROLLOUT_WIDE=0 keeps the module
@@ -571,8 +585,26 @@ class SyncStepRolloutGenerator(RolloutGenerator):
         N = self.num_envs
         params = params.contiguous().float()
         v = v.contiguous().float()
-        if self.discrete:
-            rc = L.rai_categorical_sample(params.data_ptr(), None, N, params.shape[-1], self.seed,
+        if self.multidiscrete:
+            from .md_ops import sample
+
+            nvec = self.policy.network._pi._sizes
+            if (params.is_cuda and params.shape[-1] <= _lib.RAI_GRID_MAX_A and len(nvec) <= _lib.RAI_MD_MAX_G):
+                sample(params, self.next_masks_dev if self.action_masks is not None else None, nvec, self.seed,
+                       self.rng_offset, self.actions[s], self.logprobs[s], v, self.values[s], 1)
+            else:  # beyond the sampler's limits: the head's own torch draw
+                pi = self.policy.network._pi
+                m = self.next_masks_dev if self.action_masks is not None else None
+                groups = pi._masked_groups(params, m)
+                a = torch.stack([torch.multinomial(torch.softmax(g, -1), 1).squeeze(-1) for g in groups], dim=-1)
+                from .md_ops import logp_entropy_torch
+
+                self.actions[s].copy_(a)
+                self.logprobs[s].copy_(logp_entropy_torch(params, nvec, a, m)[0])
+                self.values[s].copy_(v)
+        elif self.discrete:
+            mask = self.next_masks_dev.view(torch.uint8) if self.action_masks is not None else None
+            rc = L.rai_categorical_sample(params.data_ptr(), _lib.ptr(mask), N, params.shape[-1], self.seed,
                                           self.rng_offset, self.actions[s].data_ptr(), self.logprobs[s].data_ptr(),
                                           v.data_ptr(), self.values[s].data_ptr(), 1, st)
             _lib.check(rc, "rai_categorical_sample")
@@ -613,11 +645,13 @@ class SyncStepRolloutGenerator(RolloutGenerator):
                 self._gridnet_step(s)
             elif self.sde is not None:
                 self._sde_sample(*self._policy_forward(net.sde_params_and_value), s)
+            elif self.multidiscrete:
+                self._sample(*self._policy_forward(net.md_logits_and_value), s)
             else:
                 params, v = self._policy_forward(self._wide_fwd if self._wide_fwd is not None
                                                  else net.dist_params_and_value)
                 self._sample(params, v, s)
-            src = self.actions[s] if (self.discrete or self.gridnet) else self.clamped
+            src = self.actions[s] if (self.discrete or self.gridnet or self.multidiscrete) else self.clamped
             self.h_act.copy_(src, non_blocking=True)
             self._act_ready.record()
             self._act_ready.synchronize()
