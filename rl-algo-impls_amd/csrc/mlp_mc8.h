@@ -96,7 +96,26 @@ struct SmemM8 {
   float Ps[Geo::NTILE][OUTP + 6][HID];  // per-tile partials: dW3[o], db2, db1, dW1[k]
 };
 
-// bounded spin of one lane until sync[i0] and sync[i1] both reach `want`
+// Bounded spin of the calling lanes of one wave (one lane, or the first lanes of wave 0) until every word
+// polled has reached `want`: a lane with `poll` set loads its own word, so an iteration is ONE wave
+// instruction (one relaxed agent-scope 8-byte load per polling lane) and one wait for it, and the loop
+// leaves on that load -- no second load of a counter on the way out.  False when the spin expired.
+__device__ __forceinline__ bool m8_wait(const unsigned long long* word, bool poll, unsigned long long want,
+                                        long long limit) {
+  const unsigned long long t0 = rai_clock();
+  for (;;) {
+    bool ok = true;
+    if (poll) ok = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
+    if (__all(ok)) return true;
+    // the clock is read on every failed poll, and the wave sleeps before the next one: checking the bound
+    // only every 64th failed poll, with or without the sleep, measured no faster
+    if (rai_expired(t0, limit)) return false;
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+
+// A/B builds only (-DRAI_M8_SERIAL_POLL): the waits as they were -- one lane loading both words one after
+// the other (round 1 passed its one counter twice), each load with its own wait
 __device__ __forceinline__ bool m8_wait2(unsigned long long* sync, int i0, int i1, unsigned long long want,
                                          long long limit) {
   const unsigned long long t0 = rai_clock();
@@ -589,7 +608,11 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
     STAMP(10);
     if (tid == 0) {
       __hip_atomic_fetch_add(&sync[M8_CNT1 + net], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef RAI_M8_SERIAL_POLL
       if (!m8_wait2(sync, M8_CNT1 + net, M8_CNT1 + net, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL)) {
+#else
+      if (!m8_wait(&sync[M8_CNT1 + net], true, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL)) {
+#endif
         atomicExch(a.err, 1);
         S.bail = 1;
       }
@@ -734,11 +757,25 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       __hip_atomic_store(gq, tg | (u >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(gq + 1, tg | (u & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(&sync[M8_CNT2 + net], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef RAI_M8_SERIAL_POLL
       if (!m8_wait2(sync, M8_CNT2, M8_CNT2 + 1, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL)) {
         atomicExch(a.err, 1);
         S.bail = 1;
       }
-    } else if (w == 3 && mb + 1 < nmb) {
+#endif
+    }
+#ifndef RAI_M8_SERIAL_POLL
+    if (w == 0) {
+      // both networks' round-2 counters, one wave instruction per poll: lane 0 loads the actor's word and
+      // lane 1 the critic's (adjacent), after lane 0's own arrival above
+      const int ln = tid & 63;
+      if (!m8_wait(&sync[M8_CNT2 + (ln & 1)], ln < 2, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL) && ln == 0) {
+        atomicExch(a.err, 1);
+        S.bail = 1;
+      }
+    }
+#endif
+    if (w == 3 && mb + 1 < nmb) {
       pf_store();  // the next step's rows -> LDS (this step's px / p* reads all preceded round 1)
     }
     __syncthreads();
