@@ -406,6 +406,39 @@ int rai_ppo_loss(const float* new_logp, const float* entropy, int64_t n_entropy,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
+ * The PPO loss with the teacher-KL term (rl_algo_impls/loss/teacher_kl_loss.py,
+ * ppo.py:363-371) fused into the same row loop: rai_ppo_loss's launch (one
+ * workgroup; 256 threads up to B = 2048, else 1024) with one more per-row
+ * input.  With l = new_logp, o = old_logp, t = teacher_logp, d = t - l and
+ * r = exp(l - o), a row is f = (exp(d) - 1) - d (unbiased) or 0.5 d^2, times r
+ * under importance sampling (r carries gradient); the loss gains
+ * coef * mean_b(row) before the grad_scale factor, untouched by the kl_cutoff
+ * latch, and d_logp gains the term's gradient.  The block lives in device
+ * memory (a replayed hipGraph reads the coefficient the host last uploaded);
+ * a coefficient of exactly 0 switches the term off, and d_logp / the stats row
+ * are then bit-identical to rai_ppo_loss's.
+ *
+ * teacher_stats (device, max_stats floats, may be NULL): the un-scaled term at
+ * [state->stat_index], next to the stats row (0 when the coefficient is 0).
+ * loss_kind: the loss hp holds, stated by the caller because hp is device
+ * memory; the term exists for PPO only: anything but 0, or a NULL old_logp,
+ * is RAI_E_MODE.  NULL teacher_logp or tk: RAI_E_NULLPTR.
+ * ------------------------------------------------------------------------ */
+typedef struct rai_teacher_kl {
+  float coef;                  /* ppo.py:371 teacher_kl_loss_coef; 0: term off */
+  int32_t unbiased;            /* teacher_kl_loss.py:43-47 */
+  int32_t importance_sampling; /* ppo.py:368 teacher_loss_importance_sampling */
+} rai_teacher_kl;
+
+int rai_ppo_loss_teacher(const float* new_logp, const float* entropy, int64_t n_entropy,
+                         const float* new_values, const float* old_logp, const float* old_values,
+                         const float* advantages, const float* returns, int64_t B, int32_t K,
+                         const rai_ppo_hparams* hp, rai_train_state* state, float* d_logp,
+                         float* d_entropy, float* d_values, float* stats, int32_t max_stats,
+                         const float* teacher_logp, const rai_teacher_kl* tk, float* teacher_stats,
+                         int32_t loss_kind, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
  * Fused clip_grad_norm_ + optimizer step over one flat fp32 parameter buffer.
  * Replaces rl_algo_impls/ppo/ppo.py:441-447 (clip_grad_norm_(...).item(),
  * Adam(eps=1e-7).step(), zero_grad) and rl_algo_impls/a2c/a2c.py:202-205

@@ -23,6 +23,7 @@ _LAZY = {
     "SyncStepRolloutGenerator": "rollout",
     "DeviceRollout": "rollout",
     "Batch": "rollout",
+    "TeacherKLLoss": "teacher_kl",
     "ALGOS": "registry",
     "ALL_ALGOS": "registry",
     "POLICIES": "registry",

@@ -70,6 +70,12 @@ class PPOHparams(C.Structure):
     ]
 
 
+class TeacherKL(C.Structure):
+    """Mirror of rai_teacher_kl (the teacher-KL term's device-resident block)."""
+
+    _fields_ = [("coef", C.c_float), ("unbiased", C.c_int32), ("importance_sampling", C.c_int32)]
+
+
 class MinibatchDesc(C.Structure):
     """Mirror of rai_minibatch_desc."""
 
@@ -168,6 +174,8 @@ _SIGNATURES = {
     "rai_ppo_loss_workspace_bytes": (_i64, [_i64, _i32]),
     "rai_ppo_loss": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                                _vp, _i32, _vp, _i64, _vp]),
+    "rai_ppo_loss_teacher": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "rai_optim_workspace_bytes": (_i64, [_i64]),
     "rai_clip_optim_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "rai_gather_rows": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _vp]),

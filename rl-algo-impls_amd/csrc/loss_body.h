@@ -28,6 +28,17 @@ struct LossArgs {
   int32_t max_stats;
 };
 
+// The teacher-KL instantiation's arguments (rl_algo_impls/loss/teacher_kl_loss.py; ppo.py:363-371): the
+// loss arguments plus the teacher's per-row log-probabilities, the device-resident rai_teacher_kl block
+// and a table of the un-scaled term, one float per stats row (indexed and bounded like the stats rows).
+struct TeacherLossArgs : LossArgs {
+  const float* teacher_logp;
+  const rai_teacher_kl* tk;
+  float* teacher_stats;
+};
+template <bool TEACHER> struct loss_args_for { using type = LossArgs; };
+template <> struct loss_args_for<true> { using type = TeacherLossArgs; };
+
 struct AdvNorm {
   float mean[RAI_MAX_K];
   float inv_den[RAI_MAX_K];  // unused: keep (x - mean) / den as torch does
@@ -111,10 +122,15 @@ __device__ __forceinline__ float row_adv(const LossArgs& a, const rai_ppo_hparam
 
 // The loss body over one workgroup (blockDim.x threads) owning the minibatch: shared by
 // pg_loss_kernel (loss.hip) and the wide-MLP head+loss kernel (mlp_wide.hip).
-template <int KM>
-__device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
+// TEACHER (loss_teacher.hip's rai_ppo_loss_teacher only) adds the teacher-KL term: with d = t - l and
+// r = exp(l - o), the row is f = (exp(d) - 1) - d (unbiased) or 0.5 d^2, times r under importance
+// sampling (r NOT detached); coef * mean(row) joins the loss untouched by the kl_cutoff latch.  Every
+// TEACHER branch is `if constexpr`: the instantiations without it compile to what they were.
+template <int KM, bool TEACHER = false>
+__device__ __forceinline__ void pg_loss_body(const typename loss_args_for<TEACHER>::type& a) {
 #pragma clang fp contract(off)
-  constexpr int NR = 4 + 2 * KM;  // pi_sum, kl_sum, clip_cnt, ent_sum, vloss[KM], vclip[KM]
+  // pi_sum, kl_sum, clip_cnt, ent_sum, vloss[KM], vclip[KM] (, teacher row sum)
+  constexpr int NR = 4 + 2 * KM + (TEACHER ? 1 : 0);
   __shared__ double red[NR * (LOSS_THREADS / 64 + 1)];
   __shared__ AdvNorm nm_s;
   // by value: one scalar load batch at entry (through a reference every field read after a barrier is a
@@ -122,6 +138,18 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
   // at the very end
   const rai_ppo_hparams hp = *a.hp;
   const int st_stat_index = a.state->stat_index, st_pi_coef_zero = a.state->pi_coef_zero;
+  // the teacher block by value too: the step is replayed from a hipGraph, so a scheduled coefficient
+  // arrives through device memory.  A coefficient of exactly 0 switches the term off: every store below
+  // is then the one rai_ppo_loss makes
+  float t_coef = 0.f;
+  bool t_unbiased = true, t_is = true;
+  if constexpr (TEACHER) {
+    const rai_teacher_kl tk = *a.tk;
+    t_coef = tk.coef;
+    t_unbiased = tk.unbiased != 0;
+    t_is = tk.importance_sampling != 0;
+  }
+  const bool t_on = TEACHER && t_coef != 0.f;
   const int K = a.K;
   const int64_t B = a.B;
   const int tid = threadIdx.x, NT = blockDim.x;
@@ -132,7 +160,7 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
   // pass.  Otherwise the accessors read memory, as before.  Same values, same arithmetic.
   const bool one_row = B <= NT;
   float c_adv[KM], c_v[KM], c_R[KM], c_vo[KM];
-  float c_nl = 0.f, c_ol = 0.f, c_ent = 0.f;
+  float c_nl = 0.f, c_ol = 0.f, c_ent = 0.f, c_tl = 0.f;
 #pragma unroll
   for (int k = 0; k < KM; ++k) c_adv[k] = c_v[k] = c_R[k] = c_vo[k] = 0.f;
   if (one_row && tid < B) {
@@ -146,6 +174,7 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
       }
     c_nl = a.new_logp[tid];
     c_ol = a.old_logp[tid];
+    if constexpr (TEACHER) c_tl = a.teacher_logp[tid];
   }
   const bool one_ent = a.n_entropy <= NT;
   if (one_ent && tid < a.n_entropy) c_ent = a.entropy[tid];
@@ -155,6 +184,10 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
   auto OV = [&](int64_t b, int k) -> float { return one_row ? c_vo[k] : a.old_values[b * K + k]; };
   auto NL = [&](int64_t b) -> float { return one_row ? c_nl : a.new_logp[b]; };
   auto OL = [&](int64_t b) -> float { return one_row ? c_ol : a.old_logp[b]; };
+  auto TL = [&](int64_t b) -> float {
+    if constexpr (TEACHER) return one_row ? c_tl : a.teacher_logp[b];
+    else return 0.f;
+  };
 
   // ---- pass 0: advantage moments (two-pass, fp64 accumulation; ppo.py:307-318) ---------
   const bool need_cols = !hp.normalize_after_scaling && (hp.normalize_advantage || hp.standardize_advantage);
@@ -265,6 +298,14 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
       acc[0] += (double)fminf(ratio * A, cr * A);
       acc[1] += (double)((ratio - 1.f) - logratio);
       acc[2] += (fabsf(ratio - 1.f) > hp.clip_range) ? 1.0 : 0.0;
+      if constexpr (TEACHER) {
+        if (t_on) {  // teacher_kl_loss.py:41-49, in its order of operations
+          const float d = TL(b) - NL(b);
+          float f = t_unbiased ? (expf(d) - 1.f) - d : 0.5f * (d * d);
+          if (t_is) f = f * ratio;
+          acc[NR - 1] += (double)f;
+        }
+      }
     } else {
       acc[0] += (double)(A * NL(b));
     }
@@ -300,6 +341,7 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
 
   // ---- pass 2: gradients to the network outputs (torch.min/max tie split, clamp closed) --
   const float g_pi = (-pi_coef * invB) * gs;
+  [[maybe_unused]] const float g_t = (t_coef * invB) * gs;
   float gl[KM];
 #pragma unroll
   for (int k = 0; k < KM; ++k) gl[k] = ((hp.vf_coef[k] * halve) * invB) * gs;  // d loss / d l_bk
@@ -316,7 +358,17 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
       else { g1 = g_pi * 0.5f; g2 = g_pi * 0.5f; }
       const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
       const float d_ratio = g1 * A + (g2 * A) * in_clip;
-      a.d_logp[b] = d_ratio * ratio;
+      float d_lp = d_ratio * ratio;
+      if constexpr (TEACHER) {
+        if (t_on) {  // d(row)/dl in closed form; the ratio carries gradient (not detached)
+          const float d = TL(b) - NL(b);
+          float dl;
+          if (t_is) dl = t_unbiased ? -(ratio * d) : ratio * (0.5f * (d * d) - d);
+          else dl = t_unbiased ? 1.f - expf(d) : -d;
+          d_lp += g_t * dl;
+        }
+      }
+      a.d_logp[b] = d_lp;
     } else {
       a.d_logp[b] = ((-invB) * gs) * A;
     }
@@ -365,7 +417,12 @@ __device__ __forceinline__ void pg_loss_body(const LossArgs& a) {
         }
       }
     }
-    const float loss = (pi_coef * pi_loss + hp.ent_coef * ent_loss + vsum) * gs;
+    float loss = (pi_coef * pi_loss + hp.ent_coef * ent_loss + vsum) * gs;
+    if constexpr (TEACHER) {
+      const float term = t_on ? (float)(acc[NR - 1] / (double)B) : 0.f;
+      if (t_on) loss = ((pi_coef * pi_loss + hp.ent_coef * ent_loss + vsum) + t_coef * term) * gs;
+      if (a.teacher_stats && idx < a.max_stats) a.teacher_stats[idx] = term;
+    }
     if (row) {
       row[0] = loss;
       row[1] = pi_loss;

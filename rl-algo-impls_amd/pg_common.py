@@ -68,11 +68,14 @@ class TrainStats:  # rl_algo_impls/ppo/ppo.py:36-99
 
 
 class DeviceBlocks:
-    """HBM copies of rai_ppo_hparams and rai_train_state + the stats/norm tables."""
+    """HBM copies of rai_ppo_hparams, rai_train_state and rai_teacher_kl + the stats/norm tables (and the
+    teacher-KL term's table, one float per stats row)."""
 
     def __init__(self, device: torch.device):
         self.device = device
         self.hp = torch.empty(C.sizeof(_lib.PPOHparams), dtype=torch.uint8, device=device)
+        self.teacher = torch.zeros(C.sizeof(_lib.TeacherKL), dtype=torch.uint8, device=device)
+        self.teacher_stats = torch.zeros((1,), dtype=torch.float32, device=device)
         self.state = torch.empty(C.sizeof(_lib.TrainState), dtype=torch.uint8, device=device)
         self.stats = torch.zeros((1, _lib.RAI_STAT_STRIDE), dtype=torch.float32, device=device)
         self.norms = torch.zeros((1,), dtype=torch.float32, device=device)
@@ -81,11 +84,17 @@ class DeviceBlocks:
     def ensure_tables(self, n_stats: int, n_norms: int) -> None:
         if self.stats.shape[0] < n_stats:
             self.stats = torch.zeros((n_stats, _lib.RAI_STAT_STRIDE), dtype=torch.float32, device=self.device)
+            self.teacher_stats = torch.zeros((n_stats,), dtype=torch.float32, device=self.device)
         if self.norms.shape[0] < n_norms:
             self.norms = torch.zeros((n_norms,), dtype=torch.float32, device=self.device)
 
-    def upload(self, hp: _lib.PPOHparams, opt_step: int) -> None:
+    def upload(self, hp: _lib.PPOHparams, opt_step: int, teacher: Optional[_lib.TeacherKL] = None) -> None:
+        """Once per update: what a replayed minibatch step reads from device memory.  teacher: the
+        teacher-KL block (coefficient and variant) when the update launches rai_ppo_loss_teacher, so a
+        scheduled coefficient reaches the captured graph."""
         struct_to_device(hp, self.device, self.hp)
+        if teacher is not None:
+            struct_to_device(teacher, self.device, self.teacher)
         struct_to_device(_lib.TrainState(opt_step=opt_step, stat_index=0, pi_coef_zero=0, norm_index=0),
                          self.device, self.state)
 
@@ -144,10 +153,23 @@ def make_hparams(*, loss_kind: int, K: int, clip_range=0.2, clip_range_vf=None, 
     return hp
 
 
-def launch_loss(blocks: DeviceBlocks, logp, ent, v, old_logp, old_values, adv, ret, K: int):
+def launch_loss(blocks: DeviceBlocks, logp, ent, v, old_logp, old_values, adv, ret, K: int, teacher_logp=None):
+    """The fused loss launch; teacher_logp (B): rai_ppo_loss_teacher with blocks.teacher / teacher_stats."""
     d_logp, d_ent, d_v = blocks.grad_buffers(logp, ent, v)
     B = int(logp.shape[0])
     logp_c, ent_c, v_c = logp.detach().contiguous(), ent.detach().contiguous(), v.detach().contiguous()
+    if teacher_logp is not None:
+        assert blocks.teacher_stats.shape[0] == blocks.stats.shape[0]
+        rc = _lib.lib().rai_ppo_loss_teacher(
+            logp_c.data_ptr(), ent_c.data_ptr(), ent_c.numel(), v_c.data_ptr(),
+            None if old_logp is None else old_logp.contiguous().data_ptr(),
+            None if old_values is None else old_values.contiguous().data_ptr(),
+            adv.contiguous().data_ptr(), ret.contiguous().data_ptr(), B, K, blocks.hp.data_ptr(),
+            blocks.state.data_ptr(), d_logp.data_ptr(), d_ent.data_ptr(), d_v.data_ptr(), blocks.stats.data_ptr(),
+            int(blocks.stats.shape[0]), teacher_logp.contiguous().data_ptr(), blocks.teacher.data_ptr(),
+            blocks.teacher_stats.data_ptr(), 0, None, 0, _lib.stream_handle(logp.device))
+        _lib.check(rc, "rai_ppo_loss_teacher")
+        return d_logp, d_ent, d_v
     rc = _lib.lib().rai_ppo_loss(
         logp_c.data_ptr(), ent_c.data_ptr(), ent_c.numel(), v_c.data_ptr(),
         None if old_logp is None else old_logp.contiguous().data_ptr(),

@@ -45,9 +45,16 @@ class PPO:
                  teacher_kl_loss_coef=None, teacher_kl_loss_fn=None, teacher_loss_importance_sampling=True):
         unsupported(freeze_policy_head=freeze_policy_head, freeze_value_head=freeze_value_head,
                     freeze_backbone=freeze_backbone, switch_range=switch_range is not None,
-                    guide_probability=guide_probability is not None, autocast_loss=autocast_loss,
-                    teacher_kl_loss_coef=teacher_kl_loss_coef is not None)
+                    guide_probability=guide_probability is not None, autocast_loss=autocast_loss)
         assert not (normalize_advantage and standardize_advantage), "Cannot both normalize and standardize advantage"
+        # the teacher-KL term (ppo.py:188-190,363-371): on when the coefficient is truthy; the loss fn's
+        # add_to_batch runs after every rollout whenever the fn is set
+        assert not teacher_kl_loss_coef or teacher_kl_loss_fn is not None, \
+            "teacher_kl_loss_coef needs a teacher_kl_loss_fn (TeacherKLLoss)"
+        self.teacher_kl_loss_coef = teacher_kl_loss_coef
+        self.teacher_kl_loss_fn = teacher_kl_loss_fn
+        self.teacher_loss_importance_sampling = teacher_loss_importance_sampling
+        self._teacher_stats: Optional[np.ndarray] = None
         self.policy = policy
         self.device = torch.device(device)
         self.tb_writer = tb_writer
@@ -530,9 +537,13 @@ class PPO:
             chart["reward_weights"] = self.multi_reward_weights
         if self.vf_weights is not None:
             chart["vf_weights"] = self.vf_weights
+        if self.teacher_kl_loss_coef is not None:
+            chart["teacher_kl_loss_coef"] = self.teacher_kl_loss_coef
         log_scalars(self.tb_writer, "charts", chart, timesteps_elapsed)
 
         r = rollout_generator.rollout(gamma=self.gamma, gae_lambda=self.gae_lambda)
+        if self.teacher_kl_loss_fn:  # ppo.py:259-262
+            r.add_to_batch(self.teacher_kl_loss_fn.add_to_batch, rollout_generator.vec_env.num_envs)
         self.last_rollout_seconds = perf_counter() - start_time  # host env + policy steps (synced per step)
         timesteps_elapsed += r.total_steps
         stats, norms, K = self.update(r)
@@ -560,7 +571,7 @@ class PPO:
         head); None otherwise (the generic per-minibatch path then runs)."""
         from .policy import mlp_actor_critic_spec
 
-        if self.force_generic:
+        if self.force_generic or self._teacher_on():  # the epoch kernels carry no teacher term
             return None
         spec = mlp_actor_critic_spec(self.policy)
         if spec is None or self.batch_size < 2:
@@ -674,6 +685,8 @@ class PPO:
         if not hasattr(r, "epoch_batch") or (self.dp_enabled and self._xdp is None):
             return None
         if getattr(r, "action_masks", None) is not None:  # the kernel has no mask input
+            return None
+        if self._teacher_on():  # nor a teacher term
             return None
         if not self._wide_epoch_options_ok():
             return None
@@ -819,6 +832,8 @@ class PPO:
         """The wide-MLP fused step for this policy, or None (structure / options not covered)."""
         if self.force_generic or not self.use_wide or not self.flat.flat.is_cuda:
             return None
+        if self._teacher_on():  # rai_mlp_wide_forward_loss has no teacher term: the network + rai_ppo_loss_teacher
+            return None
         if self._wide is None:
             from .mlp_wide import WideStep, wide_mlp_spec
 
@@ -831,12 +846,40 @@ class PPO:
         self._wide.check_pointers()
         return self._wide
 
+    def _teacher_on(self) -> bool:
+        """The teacher-KL term is part of the loss (ppo.py:363: a truthy coefficient)."""
+        return bool(self.teacher_kl_loss_coef) and self.teacher_kl_loss_fn is not None
+
+    def _teacher_field(self, r, wide) -> Optional[torch.Tensor]:
+        """The rollout's flat teacher_logprobs when the per-minibatch path launches rai_ppo_loss_teacher:
+        the field is there (add_to_batch ran) and the loss kernel is the standalone one.  A coefficient
+        of 0 keeps the launch (the kernel then computes rai_ppo_loss's loss exactly), so a schedule that
+        reaches 0 replays the graph it captured."""
+        if self.teacher_kl_loss_fn is None or wide is not None:
+            return None
+        t = getattr(r, "additional", {}).get("teacher_logprobs")
+        if t is None:
+            if self._teacher_on():
+                raise ValueError("teacher_kl_loss_coef is set but the rollout carries no teacher_logprobs "
+                                 "(Rollout.add_to_batch with TeacherKLLoss.add_to_batch)")
+            return None
+        if self.dp_enabled and self.world > 1:
+            raise NotImplementedError("the teacher-KL term under data parallel (world > 1)")
+        return t
+
+    def _teacher_block(self) -> _lib.TeacherKL:
+        return _lib.TeacherKL(coef=float(self.teacher_kl_loss_coef or 0.0),
+                              unbiased=int(bool(self.teacher_kl_loss_fn.unbiased)),
+                              importance_sampling=int(bool(self.teacher_loss_importance_sampling)))
+
     def _minibatch_loss_grads(self, wide, obs, actions, masks, values, adv, ret, logprobs, K_box,
-                              obs_prepared: bool = False) -> None:
+                              obs_prepared: bool = False, teacher_logp=None) -> None:
         """Forward, fused loss and backward of one minibatch into the flat gradient buffer: the
         wide-MLP kernels when available, else the PyTorch network + autograd (NatureCNN layers
-        with the cnn_ops epilogues accumulating straight into the flat gradient views)."""
+        with the cnn_ops epilogues accumulating straight into the flat gradient views).
+        teacher_logp: the minibatch's teacher log-probabilities (rai_ppo_loss_teacher)."""
         if wide is not None and masks is None:
+            assert teacher_logp is None
             B = int(obs.shape[0])
             outs = self._wide_out.get(B)
             if outs is None:
@@ -856,13 +899,17 @@ class PPO:
                 logp, ent, v = self.policy(obs, actions, action_masks=masks)
             if K_box[0] is None:
                 K_box[0] = value_columns(v)
-            d_logp, d_ent, d_v = launch_loss(self.blocks, logp, ent, v, logprobs, values, adv, ret, K_box[0])
+            d_logp, d_ent, d_v = launch_loss(self.blocks, logp, ent, v, logprobs, values, adv, ret, K_box[0],
+                                             teacher_logp=teacher_logp)
             torch.autograd.backward([logp, ent, v], [d_logp, d_ent, d_v])
 
     def update(self, r) -> Tuple[np.ndarray, np.ndarray, int]:
         """All epochs x minibatches of one update, enqueued without host syncs;
         returns the per-minibatch stats rows and grad norms (one D2H copy)."""
         self.last_update_rollout = r
+        self._teacher_stats = None
+        if self._teacher_on() and self.dp_enabled and self.world > 1:
+            raise NotImplementedError("the teacher-KL term under data parallel (world > 1)")
         if self.dp_enabled and self.dp_update_mode == "replicated":
             # data parallel by replication: the whole env group's rollout on every rank, then the
             # single-process update (no exchange inside it); the ranks' weights are checked equal after
@@ -899,8 +946,9 @@ class PPO:
                 and r.logprobs is not None and not (self.dp_enabled and self.world > 1
                                                     and torch.distributed.get_backend(self.dp_group) != "nccl")):
             K = self._update_graphed(r, nmb)
-            return self._read_stats(n_steps, n_norms, K)
+            return self._read_stats(n_steps, n_norms, K, teacher=self._teacher_field(r, self._wide_step()) is not None)
         wide = self._wide_step()
+        teacher = self._teacher_field(r, wide) is not None
         shuffle = not self.gradient_accumulation
         ext = None
         for e in range(self.n_epochs):
@@ -908,7 +956,8 @@ class PPO:
                 full = r.epoch_batch(shuffle)
                 mbs = [r._batch_from([full.obs, full.actions, full.values, full.advantages, full.returns]
                                      + ([full.logprobs] if full.logprobs is not None else [])
-                                     + ([full.action_masks] if full.action_masks is not None else []),
+                                     + ([full.action_masks] if full.action_masks is not None else [])
+                                     + list(full.additional.values()),
                                      slice(i, i + self.batch_size)) for i in range(0, r.total_steps, self.batch_size)]
             else:
                 full, mbs = None, r.minibatches(self.batch_size, shuffle=shuffle)
@@ -920,7 +969,7 @@ class PPO:
                     ext = self._dp_moments_table(K, n_steps)
                     hp = self._hparams(K, nmb)
                     hp.ext_moments = ext.data_ptr() if ext is not None else None
-                    blocks.upload(hp, self.optimizer.step_count)
+                    blocks.upload(hp, self.optimizer.step_count, self._teacher_block() if teacher else None)
                     if ext is not None and full is not None:
                         self._fill_epoch_moments(ext, e, full.advantages, nmb)
                 elif ext is not None and mb is mbs[0] and full is not None:
@@ -928,7 +977,8 @@ class PPO:
                 if mb.logprobs is None:
                     raise ValueError("PPO needs rollout logprobs (include_logp=True)")
                 self._minibatch_loss_grads(wide, mb.obs, mb.actions, mb.action_masks, mb.values, mb.advantages,
-                                           mb.returns, mb.logprobs, [K])
+                                           mb.returns, mb.logprobs, [K],
+                                           teacher_logp=mb.additional["teacher_logprobs"] if teacher else None)
                 if not self.gradient_accumulation:
                     if self.dp_enabled:
                         self._all_reduce(self.flat.grad, average=True)
@@ -937,7 +987,7 @@ class PPO:
                 if self.dp_enabled:
                     self._all_reduce(self.flat.grad, average=True)
                 self.optimizer.step(blocks.state, blocks.norms)
-        return self._read_stats(n_steps, n_norms, K)
+        return self._read_stats(n_steps, n_norms, K, teacher=teacher)
 
     def _dp_moments_table(self, K: int, n_steps: int) -> Optional[torch.Tensor]:
         """Data parallel on the per-minibatch path: the global minibatches' advantage (mean, den),
@@ -957,15 +1007,23 @@ class PPO:
         small all-reduce; stream-ordered before the epoch's loss launches)."""
         ext[epoch * nmb:(epoch + 1) * nmb].copy_(self._global_adv_moments(adv_epoch, nmb))
 
-    def _read_stats(self, n_steps: int, n_norms: int, K: Optional[int]) -> Tuple[np.ndarray, np.ndarray, int]:
+    def _read_stats(self, n_steps: int, n_norms: int, K: Optional[int],
+                    teacher: bool = False) -> Tuple[np.ndarray, np.ndarray, int]:
+        """teacher: the update launched rai_ppo_loss_teacher; its table comes back in the same copy."""
         blocks = self.blocks
         stats_t = blocks.stats[:n_steps]
         if self.dp_enabled:
             stats_t = stats_t.clone()
             self._all_reduce(stats_t, average=True)
-        host = torch.cat([stats_t.reshape(-1), blocks.norms[:n_norms]]).cpu().numpy()
-        stats = host[: n_steps * _lib.RAI_STAT_STRIDE].reshape(n_steps, _lib.RAI_STAT_STRIDE)
-        return stats, host[n_steps * _lib.RAI_STAT_STRIDE:], K or 1
+        parts = [stats_t.reshape(-1), blocks.norms[:n_norms]]
+        if teacher:
+            parts.append(blocks.teacher_stats[:n_steps])
+        host = torch.cat(parts).cpu().numpy()
+        n_s = n_steps * _lib.RAI_STAT_STRIDE
+        stats = host[:n_s].reshape(n_steps, _lib.RAI_STAT_STRIDE)
+        if teacher and self._teacher_on():
+            self._teacher_stats = host[n_s + n_norms:]
+        return stats, host[n_s:n_s + n_norms], K or 1
 
     def _update_graphed(self, r, nmb: int) -> int:
         """The generic update with the minibatch step replayed from a hipGraph (graphs.py).
@@ -989,6 +1047,9 @@ class PPO:
         K_box = [None]
 
         wide = self._wide_step()
+        # the step's fields: the Batch fields and, with a teacher, its log-probabilities as the last one
+        teacher = self._teacher_field(r, wide)
+        fields = fields[:len(fields) - len(getattr(r, "additional", {}))] + ([teacher] if teacher is not None else [])
         # NatureCNN on uint8 frames: the gather emits obs.float() / range_size in channels_last
         xf = getattr(self.policy, "obs_transform", lambda o: None)(fields[0]) if wide is None else None
         xforms = [xf] + [None] * (len(fields) - 1) if xf is not None else None
@@ -999,7 +1060,8 @@ class PPO:
             if buckets is not None:
                 buckets.begin()
             self._minibatch_loss_grads(wide, obs, actions, masks, values, adv, ret, logprobs, K_box,
-                                       obs_prepared=xforms is not None)
+                                       obs_prepared=xforms is not None,
+                                       teacher_logp=bufs[-1] if teacher is not None else None)
             if buckets is not None:
                 buckets.finish(scale=1.0 / self.world)
             if optim_in_step:
@@ -1014,11 +1076,13 @@ class PPO:
         ext = self._dp_moments_table(K, self.n_epochs * nmb)
         hp = self._hparams(K, nmb)
         hp.ext_moments = ext.data_ptr() if ext is not None else None
-        blocks.upload(hp, self.optimizer.step_count)
+        blocks.upload(hp, self.optimizer.step_count, self._teacher_block() if teacher is not None else None)
         # a graph bakes in every device pointer it touches: key it on the ones that can change
         tag = (optim_in_step, wide is not None, buckets is not None, blocks.stats.data_ptr(), blocks.norms.data_ptr(), blocks.hp.data_ptr(),
                blocks.state.data_ptr(), self.flat.flat.data_ptr(), self.flat.grad.data_ptr(),
                self.optimizer.hp_dev.data_ptr())
+        if teacher is not None:
+            tag += (blocks.teacher.data_ptr(), blocks.teacher_stats.data_ptr())
         g = gu.graph_for(fields, B, tag, xforms)
         cur = torch.cuda.current_stream(self.device)
         gu.stream.wait_stream(cur)
@@ -1087,7 +1151,9 @@ class PPO:
             loss=float(last[:, 0].mean()), pi_loss=float(last[:, 1].mean()), v_loss=v_loss,
             entropy_loss=float(last[:, 2].mean()), approx_kl=float(last[:, 3].mean()),
             clipped_frac=float(last[:, 4].mean()),
-            val_clipped_frac=float(val_clipped[0]) if K == 1 else val_clipped, additional_losses={},
+            val_clipped_frac=float(val_clipped[0]) if K == 1 else val_clipped,
+            additional_losses=({"teacher_kl_loss": float(np.mean(self._teacher_stats[-nmb:].astype(np.float64)))}
+                               if self._teacher_stats is not None else {}),
             explained_var=explained_var, grad_norm=float(np.mean(last_norms)))
 
     def save(self, path: str) -> None:

@@ -199,6 +199,8 @@ class DeviceRollout(Rollout):
         self._perm_keys = perm_keys
         self._flat: Optional[List[torch.Tensor]] = None
         self._perm_bufs: Dict[int, List[torch.Tensor]] = {}
+        # add_to_batch's fields, flat (T*N, ...) on the device; Batch.additional carries them in key order
+        self.additional: Dict[str, torch.Tensor] = {}
 
     @classmethod
     def from_fields(cls, device: torch.device, obs: torch.Tensor, actions: torch.Tensor, values: torch.Tensor,
@@ -219,6 +221,7 @@ class DeviceRollout(Rollout):
         self.rewards = self.episode_starts = self.next_episode_starts = self.next_values = None
         self._perm_source, self._generator, self._perm_keys = perm_source, None, perm_keys
         self._flat, self._perm_bufs = None, {}
+        self.additional = {}
         return self
 
     # -- Rollout API ---------------------------------------------------------------------
@@ -254,8 +257,13 @@ class DeviceRollout(Rollout):
                 fields.append(fl(self.logprobs))
             if self.action_masks is not None:
                 fields.append(fl(self.action_masks))
+            fields += [self.additional[k] for k in self._additional_keys()]
             self._flat = fields
         return self._flat
+
+    def _additional_keys(self) -> List[str]:
+        """add_to_batch's keys in the fixed (sorted) order every field list and Batch.additional uses."""
+        return sorted(self.additional)
 
     def _epoch_fields(self) -> List[torch.Tensor]:
         """The fields an epoch's permuted copy carries: _flat_fields() (what the update's kernels read)
@@ -266,7 +274,8 @@ class DeviceRollout(Rollout):
         return fields
 
     def _batch_from(self, fields: List[torch.Tensor], sl: slice) -> Batch:
-        """A Batch over rows sl of fields laid out as _epoch_fields() (num_actions optional)."""
+        """A Batch over rows sl of fields laid out as _epoch_fields() (num_actions optional; the
+        additional fields present whenever the rollout has any)."""
         obs, actions, values, adv, ret = (f[sl] for f in fields[:5])
         i = 5
         logprobs = None
@@ -277,8 +286,12 @@ class DeviceRollout(Rollout):
         if self.action_masks is not None:
             masks = fields[i][sl]
             i += 1
+        additional = {}
+        for k in self._additional_keys():
+            additional[k] = fields[i][sl]
+            i += 1
         num_actions = fields[i][sl] if len(fields) > i else None
-        return Batch(obs, logprobs, actions, masks, num_actions, values, adv, ret)
+        return Batch(obs, logprobs, actions, masks, num_actions, values, adv, ret, additional)
 
     def permutation(self) -> torch.Tensor:
         if self._perm_source is not None:
@@ -302,8 +315,12 @@ class DeviceRollout(Rollout):
         flat = self._epoch_fields()
         if shuffle:
             self.alloc_epoch_buffers(slot)
-            gather_rows(flat, self._perm_bufs[slot], self.permutation())
             src = self._perm_bufs[slot]
+            perm = self.permutation()
+            # one gather launch carries RAI_MAX_FIELDS fields; more (masks, num_actions and an additional
+            # field together) take a second launch with the same permutation
+            for j in range(0, len(flat), _lib.RAI_MAX_FIELDS):
+                gather_rows(flat[j:j + _lib.RAI_MAX_FIELDS], src[j:j + _lib.RAI_MAX_FIELDS], perm)
         else:
             src = flat
         return self._batch_from(src, slice(0, self.total_steps))
@@ -314,10 +331,28 @@ class DeviceRollout(Rollout):
             sl = slice(i, i + batch_size)
             g = lambda t: None if t is None else t[sl]
             yield Batch(full.obs[sl], g(full.logprobs), full.actions[sl], g(full.action_masks), g(full.num_actions),
-                        full.values[sl], full.advantages[sl], full.returns[sl])
+                        full.values[sl], full.advantages[sl], full.returns[sl],
+                        {k: v[sl] for k, v in full.additional.items()})
 
     def add_to_batch(self, map_fn: BatchMapFn, batch_size: int) -> None:
-        raise NotImplementedError("teacher-KL additional batch fields are outside the hot-path scope")
+        """vec_rollout.py:155-164 on the device: map_fn over un-shuffled chunks of batch_size rows of the flat
+        fields (Batch views, no host copies), the results concatenated per key into (T*N, ...) tensors that
+        every later epoch copy, minibatch and Batch.additional carries."""
+        if self.rewards is None:  # from_fields: a gathered rollout has no map_fn results of its ranks
+            raise NotImplementedError("add_to_batch on a rollout assembled from fields is outside the hot-path scope")
+        self._flat = None
+        self._perm_bufs = {}
+        n = self.total_steps
+        flat = self._epoch_fields()
+        parts: Dict[str, List[torch.Tensor]] = {}
+        for i in range(0, n, batch_size):
+            for k, v in map_fn(self._batch_from(flat, slice(i, i + batch_size))).items():
+                parts.setdefault(k, []).append(v)
+        for k, vs in parts.items():
+            t = torch.cat(vs).to(self.device).contiguous()
+            assert t.shape[0] == n, f"add_to_batch field {k!r}: {t.shape[0]} rows for {n} steps"
+            self.additional[k] = t
+        self._flat = None
 
 
 _UNSUPPORTED_GEN_KW = ("num_envs_reset_every_rollout", "rolling_num_envs_reset_every_rollout",
