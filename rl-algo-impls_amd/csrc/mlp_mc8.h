@@ -29,10 +29,28 @@
 // arrives), the partial and summed-share slots go out as plain stores drained into that XCC's L2 (the
 // lines stay there; write-through drops them and the readers then fetch past the L2).  The readers'
 // loads stay sc1 (past their own L1 only) and the share norms, read by the other network's XCC, stay
-// write-through.  Placement decides only the store form, never correctness.  Slots are
-// double-buffered by minibatch parity; the reuse argument is the 4-CU one per round (a CU cannot pass round r of step k + 1 before every
-// CU that reads its round-r slot of step k has published round r + 1 of step k, or round 1 of
-// step k + 1).  Every spin is bounded by elapsed clock and sets state.err.
+// write-through.  Placement decides only the store form, never correctness.
+//
+// With one row tile per CU and one column tile per wave (G = 16; the per-rank M8Geo<8, 16>) there is no
+// P_B phase: wave w's dW2 rows [16w, 16w + 16) need dZ2 only at the (row, column) pairs the wave itself
+// formed in the loss phase, lane for lane the MFMA's A operand, and H1, complete since F1.  The wave
+// issues the 16 dW2 MFMAs at the end of its loss phase (same order as P_B: bit-identical) and stores the
+// accumulators straight to its round-1 slot (dword stores: W2 rows are LD = 66 floats, 8-byte aligned);
+// nothing waits for them until the vmcnt(0) ahead of the round-1 arrival, so the write-through of 4,224
+// of the slot's 4,752 floats drains under dH1.  After dH1 only the other 132 chunks (S.Gb) are published.
+// The two padding columns of a W2 row, which the share sums and norms include, are stored as zeros on
+// each parity slot's first step of a launch (the scratch is not zeroed per launch).  The steps are F1,
+// F2, loss + dZ2 + dW2, dH1 + small tensors, publish.
+//
+// Slots are double-buffered by minibatch parity.  Round-1 slots are now written from the loss phase of
+// step k + 2 on, not from its publish: a CU in step k + 2 has passed the round-2 wait of step k + 1, so
+// every CU of the network has arrived on round 2 of step k + 1, which each does only after its round-1
+// reads of step k + 1 and hence of step k -- every reader of the step-k slot has its data in registers.
+// (Both networks' round-2 counters are awaited, so this holds for either.)  Round-2 slots: a CU cannot
+// pass round 2 of step k + 1 before every CU that reads its round-2 slot of step k has published round
+// 1 of step k + 1.  The cross-GPU path (xworld > 1) reads and writes only summed shares, in the xGMI
+// regions between the round-1 sum and the round-2 publish; it never touches a round-1 slot and is
+// unaffected.  Every spin is bounded by elapsed clock and sets state.err.
 
 constexpr int M8_GMAX = 16;                          // largest CUs-per-network instantiation
 constexpr int M8_NT = 256;                           // threads per CU (4 waves)
@@ -135,6 +153,17 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
   constexpr int relu = RELU;
   constexpr int NPART = OUTP + 6;
   constexpr int WL_B3 = WL_W3 + OUTP * LD;
+  // One row tile per CU, one column tile per wave (G = 16, and the per-rank M8Geo<8, 16>): dW2 is formed in
+  // the loss phase from the dZ2 values the wave holds and stored from the accumulators straight to the
+  // round-1 slot (DW2_REG); see the header.  A/B builds only: -DRAI_M8_LDS_DW2 compiles the P_B phase for
+  // every geometry (the previous form).
+#ifdef RAI_M8_LDS_DW2
+  constexpr bool DW2_REG = false;
+#else
+  constexpr bool DW2_REG = NTILE == 1 && CT == 1;
+#endif
+  static_assert(WL_W2 % 4 == 0 && WL_B2 % 4 == 0, "dW2 is a whole range of float4 chunks");
+  static_assert(LD == HID + 2, "two padding columns per W2 row");
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int T = w / WPT;  // this wave's row tile (its hidden-column part: w % WPT)
@@ -375,6 +404,17 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       const int T_ = w / WPT, hf_ = w % WPT;
       const int q = li & 3;
       const int lr_ = 16 * T_ + g * 4 + q;
+      // DW2_REG: the H1 operands of this wave's dW2 rows (complete since the barrier after F1), read under
+      // the loss's transcendental chain, and the publish form of the step
+      float bvs[4][4], dzr[4];
+      int xl_ = 0;
+      if constexpr (DW2_REG) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) bvs[kk][t] = S.H1[g * 4 + kk][t * 16 + li];
+        xl_ = __builtin_amdgcn_readfirstlane(S.xl);
+      }
       float z[OUTP];
 #pragma unroll
       for (int o = 0; o < OUTP; ++o) {
@@ -415,6 +455,49 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
           const float dz = dh * act_d(relu, h2[tt][r]);
           pb2[tt] += dz;
           S.Z2[16 * T_ + g * 4 + r][16 * t + li] = dz;
+          if constexpr (DW2_REG) dzr[r] = dz;
+        }
+      }
+      if constexpr (DW2_REG) {
+        // ---- dW2 rows [16w, 16w + 16) over the CU's 16 rows: the A operand of row g * 4 + kk, column
+        // 16w + li, is the dz this lane just formed at r == kk (what P_B read back from S.Z2); the same
+        // 16 MFMAs in the same order (kk outer, t inner, one accumulator per t), so the same bits
+        f4 gacc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) gacc[t] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            gacc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(dzr[kk], bvs[kk][t], gacc[t], 0, 0, 0);
+        }
+        {
+          // straight to this CU's round-1 slot (weight-layout offsets; the step's store form), drained only
+          // by the vmcnt(0) ahead of the arrival: the write-through runs under dH1
+          const int so = (((net * 2 + par) * G + c) * WL_N + WL_W2 + (w * 16 + g * 4) * LD + li) * (int)sizeof(float);
+          if (xl_) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gacc[t][r]), srs,
+                                                      so + (r * LD + t * 16) * (int)sizeof(float), 0, 0);
+          } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gacc[t][r]), srs,
+                                                      so + (r * LD + t * 16) * (int)sizeof(float), 0, 16);
+          }
+          // the two padding columns of each W2 row (part of the share sums and norms): the slots are not
+          // zeroed per launch, so each parity's slot gets them on its first step, ahead of that arrival
+          if (mb < 2 && lane < 16) {
+            typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+            const int po = (((net * 2 + par) * G + c) * WL_N + WL_W2 + (w * 16 + lane) * LD + HID) * (int)sizeof(float);
+            if (xl_) __builtin_amdgcn_raw_buffer_store_b64(u2v{0u, 0u}, srs, po, 0, 0);
+            else __builtin_amdgcn_raw_buffer_store_b64(u2v{0u, 0u}, srs, po, 0, 16);
+          }
         }
       }
     }
@@ -515,6 +598,8 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
     lds_barrier();
     STAMP(4);
     // ============ P_B: dW2 partial over the CU's RC rows (wave w: dW2 rows [16w, 16w + 16)) =====
+    // (not with DW2_REG: dW2 left the loss phase, and the small tensors are in S.Gb since the barrier above)
+    if constexpr (!DW2_REG) {
     {
       RELANE();
       f4 gacc[4];
@@ -581,8 +666,24 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
     STAMP(19);  // work done; the barrier wait follows
     lds_barrier();
     STAMP(5);
+    }
     // ============ round 1: publish the partial (sc1), arrive; sum share c over the G slots ============
-    {
+    if constexpr (DW2_REG) {
+      // dW2 is on its way since the loss phase: what remains are the chunks outside [WL_W2, WL_B2) (W1, b1;
+      // b2, W3, b3 and the tail padding), at most one per thread
+      RELANE();
+      constexpr int C0 = WL_W2 / 4, C1 = WL_B2 / 4, NS = C0 + WL_CH - C1;
+      static_assert(NS <= M8_NT, "one small-tensor chunk per thread");
+      const int sbase = ((net * 2 + par) * G + c) * WL_N * (int)sizeof(float);
+      const int ch = min(tid < C0 ? tid : tid + (C1 - C0), WL_CH - 1);
+      const f4 pv = *reinterpret_cast<const f4*>(&S.Gb[4 * ch]);
+      if (__builtin_amdgcn_readfirstlane(S.xl)) {
+        if (tid < NS) __builtin_amdgcn_raw_buffer_store_b128(as_u4(pv), srs, sbase + 16 * ch, 0, 0);
+      } else {
+        if (tid < NS) __builtin_amdgcn_raw_buffer_store_b128(as_u4(pv), srs, sbase + 16 * ch, 0, 16);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY wave drains: its dW2 rows, its chunks here
+    } else {
       RELANE();
       const int sbase = ((net * 2 + par) * G + c) * WL_N * (int)sizeof(float);
       f4 pv[MC_CPT];

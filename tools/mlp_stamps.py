@@ -8,7 +8,9 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-os.environ["RAI_AMD_LIB"] = str(ROOT / "rl-algo-impls_amd" / "lib" / "librai_amd_stamps.so")
+# RAI_STAMPS_LIB: another stamps build (e.g. build.py alt with RAI_ALT_FLAGS="-DRAI_STAMPS -DRAI_M8_LDS_DW2")
+os.environ["RAI_AMD_LIB"] = os.environ.get("RAI_STAMPS_LIB",
+                                           str(ROOT / "rl-algo-impls_amd" / "lib" / "librai_amd_stamps.so"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -23,7 +25,8 @@ from rl_algo_impls_amd.rollout import SyncStepRolloutGenerator  # noqa: E402
 
 LAYOUT = os.environ.get("RAI_MLP_LAYOUT", "mc8")
 NAMES = {
-    "mc8": ["F1 (own columns) + barrier", "F2 + output partials + barrier", "loss + dZ2 + barrier",
+    # G = 16 forms dW2 in the loss phase (from registers, stored to the slot there) and has no P_B phase: 0 ticks
+    "mc8": ["F1 (own columns) + barrier", "F2 + output partials + barrier", "loss + dZ2 (+ dW2) + barrier",
             "dH1 + dZ1 + partials + barrier", "P_B dW2 + sums + barrier", "round 1: publish + counter wait",
             "share sum + round 2 publish + wait", "all-gather + norm + adam + barrier"],
     "mc4": ["F1+F2 forward", "out layer + loss + dZ2", "dH1 + partials + barrier", "P_B dW2 + sums",
@@ -72,7 +75,7 @@ for net in range(2):
     if LAYOUT == "mc8":  # compute phases split into work and barrier wait
         for i, n in ((15, "F1 work"), (16, "F2 work"), (17, "loss work"), (18, "dH1 work"), (19, "P_B work")):
             print(f"  {n:34s} {st[net, i] / nmb:10.1f} ticks/mb (+ barrier {st[net, i - 14] / nmb:.1f})")
-        for i, n in ((9, "  r1: wave-0 partial stores + drain"), (10, "  r1: barrier (other waves' drains)"),
+        for i, n in ((9, "  r1: wave-0 stores + drain"), (10, "  r1: barrier (other waves' drains)"),
                      (6, "  r1: counter wait + stats"), (11, "  r2: share-sum loads (+ xGMI)"),
                      (12, "  r2: share store + norm + drain"), (13, "  r2: barrier (other waves' drains)"),
                      (7, "  r2: counter wait (both networks)"), (14, "  ag: gradient + norm loads, norm sum"),
