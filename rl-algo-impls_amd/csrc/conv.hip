@@ -64,9 +64,6 @@ struct ConvFwdArgs {
 // VALU operations per byte and no LDS; the host launches it only when u8_div_valu_exact(d) has
 // checked it equal, bit for bit, to u / d for all 256 bytes (true for d = 255).
 __device__ __forceinline__ f4 u8x4_div(unsigned u, float d, float inv) {
-#ifdef RAI_U8_FAKE_CVT  // diagnostic builds only (wrong values): the dword operand path without the quotient
-  return f4{__uint_as_float(u), __uint_as_float(u >> 8), __uint_as_float(u >> 16), __uint_as_float(u >> 24)};
-#endif
   // packed-fp32 pairs (v_pk_mul_f32 / v_pk_fma_f32: two lanes' worth per VALU op, per-element IEEE results
   // identical to the scalar ops the host check runs)
   typedef float f2v __attribute__((ext_vector_type(2)));
@@ -1171,24 +1168,12 @@ __global__ __launch_bounds__(NT) void conv_dgrad_img_kernel(const ConvDgradArgs 
   for (int t = 0; t < TC; ++t) {
     const int th = t / TW, tw = t - th * TW;
     const int toff = (a.S * th * a.W + a.S * tw) * CP;
-#ifdef RAI_DGRAD_BATCH_COL2IM
-    // one tap's tiles touch distinct dx pixels: all their reads, then the adds, then the writes (one LDS
-    // round trip per tap instead of one per tile)
-    f4 cur[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-      if (pv[mt]) cur[mt] = *reinterpret_cast<const f4*>(dxl + pbase[mt] + toff);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-      if (pv[mt]) *reinterpret_cast<f4*>(dxl + pbase[mt] + toff) = cur[mt] + acc[t][mt];
-#else
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       if (!pv[mt]) continue;
       f4* d = reinterpret_cast<f4*>(dxl + pbase[mt] + toff);
       *d += acc[t][mt];
     }
-#endif
   }
   __syncthreads();
   float* dxn = a.dx + (int64_t)n * HW * a.Ci;

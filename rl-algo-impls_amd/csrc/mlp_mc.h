@@ -5,7 +5,7 @@
 // Why more than one CU per network: one CU per network is bound by its own MFMA pipe and by
 // the latency of a long dependent chain per minibatch (~33 us per minibatch at 256 rows).  Here
 // each network runs on G = 4 CUs; CU c owns minibatch rows [64c, 64c + 64), one 16-row tile per
-// wave, computed end to end as in the row-tile layout (forward, loss, dZ2, dH1, dZ1 wave-local).
+// wave, which the wave computes end to end (forward, loss, dZ2, dH1, dZ1 wave-local).
 // Per minibatch the G CUs of a network all-reduce their partial gradients:
 //   * each CU writes its partial (in the LDS weight layout, 19 KB) to a global slot with 16-B
 //     write-through (sc1) stores, drains (vmcnt(0)), meets its workgroup barrier and bumps the

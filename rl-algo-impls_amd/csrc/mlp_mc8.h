@@ -132,19 +132,6 @@ __device__ __forceinline__ bool m8_wait(const unsigned long long* word, bool pol
   }
 }
 
-// A/B builds only (-DRAI_M8_SERIAL_POLL): the waits as they were -- one lane loading both words one after
-// the other (round 1 passed its one counter twice), each load with its own wait
-__device__ __forceinline__ bool m8_wait2(unsigned long long* sync, int i0, int i1, unsigned long long want,
-                                         long long limit) {
-  const unsigned long long t0 = rai_clock();
-  while (__hip_atomic_load(&sync[i0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want ||
-         __hip_atomic_load(&sync[i1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-    if (rai_expired(t0, limit)) return false;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return true;
-}
-
 template <int OUTP, bool ACTOR, int RELU, int G, int RCV>
 __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& S, const int c) {
   using Geo = M8Geo<G, RCV>;
@@ -155,13 +142,8 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
   constexpr int WL_B3 = WL_W3 + OUTP * LD;
   // One row tile per CU, one column tile per wave (G = 16, and the per-rank M8Geo<8, 16>): dW2 is formed in
   // the loss phase from the dZ2 values the wave holds and stored from the accumulators straight to the
-  // round-1 slot (DW2_REG); see the header.  A/B builds only: -DRAI_M8_LDS_DW2 compiles the P_B phase for
-  // every geometry (the previous form).
-#ifdef RAI_M8_LDS_DW2
-  constexpr bool DW2_REG = false;
-#else
+  // round-1 slot (DW2_REG); see the header.  Every other geometry forms dW2 in the P_B phase.
   constexpr bool DW2_REG = NTILE == 1 && CT == 1;
-#endif
   static_assert(WL_W2 % 4 == 0 && WL_B2 % 4 == 0, "dW2 is a whole range of float4 chunks");
   static_assert(LD == HID + 2, "two padding columns per W2 row");
   const int tid = threadIdx.x;
@@ -709,15 +691,10 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
     STAMP(10);
     if (tid == 0) {
       __hip_atomic_fetch_add(&sync[M8_CNT1 + net], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef RAI_M8_SERIAL_POLL
-      if (!m8_wait2(sync, M8_CNT1 + net, M8_CNT1 + net, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL)) {
-#else
       if (!m8_wait(&sync[M8_CNT1 + net], true, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL)) {
-#endif
         atomicExch(a.err, 1);
         S.bail = 1;
       }
-#ifndef RAI_M8_NO_XCC_LOCAL
       if (mb == 0) {
         // every CU of the network registered its XCC before its step-0 arrival: from step 1 on, when they
         // all share one XCC (one L2), the gradient slots go out as plain stores (drained into that L2)
@@ -726,7 +703,6 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
             __hip_atomic_fetch_or(&sync[M8_XCC + net], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         S.xl = m != 0 && (m & (m - 1)) == 0;
       }
-#endif
     } else if (w == 1) {
       // while wave 0 waits for the other CUs: this CU's loss statistics (fp64 sums over its rows in
       // row order of the lanes); CU 0 turns them into rows at the end.  Off the gradient's path.
@@ -764,13 +740,9 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       const int chl = min(ch, WL_CH - 1);
       const int pbase = (net * 2 + par) * G * WL_N * (int)sizeof(float);
       f4 v[G];
-#ifdef RAI_M8_ALL_LOAD  // A/B builds only: every lane loads (clamped), as before round 4
-      const bool ld = true;
-#else
-      // only the share's owner lanes load (tid < SH: 75 of 256 at G = 16): the other lanes' clamped loads
-      // were a second copy of the request stream through the CU's address unit, results unused
+      // only the share's owner lanes load (tid < SH: 75 of 256 at G = 16): clamped loads by the other lanes
+      // would be a second copy of the request stream through the CU's address unit, results unused
       const bool ld = tid < SH;
-#endif
       if (ld) {
 #pragma unroll
         for (int cc = 0; cc < G; ++cc)
@@ -858,14 +830,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       __hip_atomic_store(gq, tg | (u >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(gq + 1, tg | (u & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(&sync[M8_CNT2 + net], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef RAI_M8_SERIAL_POLL
-      if (!m8_wait2(sync, M8_CNT2, M8_CNT2 + 1, (unsigned long long)G * (mb + 1), MC_WAIT_LOCAL)) {
-        atomicExch(a.err, 1);
-        S.bail = 1;
-      }
-#endif
     }
-#ifndef RAI_M8_SERIAL_POLL
     if (w == 0) {
       // both networks' round-2 counters, one wave instruction per poll: lane 0 loads the actor's word and
       // lane 1 the critic's (adjacent), after lane 0's own arrival above
@@ -875,7 +840,6 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
         S.bail = 1;
       }
     }
-#endif
     if (w == 3 && mb + 1 < nmb) {
       pf_store();  // the next step's rows -> LDS (this step's px / p* reads all preceded round 1)
     }
@@ -926,16 +890,6 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
         const int ch = tid + M8_NT * i;
         {
           f4 p = *reinterpret_cast<const f4*>(&S.Wt[4 * min(ch, WL_CH - 1)]);
-#ifdef RAI_M8_SCALAR_ADAM  // A/B builds only: one element per VALU op
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float pq = p[q], mq = mreg[i][q], vq = vreg[i][q];
-            adam_update_fast(pq, mq, vq, gr[i][q] * coef, w1, w2, beta2, inv_bc2_sqrt, neg_step, adam_eps);
-            p[q] = pq;
-            mreg[i][q] = mq;
-            vreg[i][q] = vq;
-          }
-#else
           const f2a C2 = {coef, coef};
 #pragma unroll
           for (int h = 0; h < 2; ++h) {  // element pairs (0, 1), (2, 3)
@@ -950,7 +904,6 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
             vreg[i][2 * h] = vv.x;
             vreg[i][2 * h + 1] = vv.y;
           }
-#endif
           if (ch < WL_CH) *reinterpret_cast<f4*>(&S.Wt[4 * ch]) = p;
         }
       }

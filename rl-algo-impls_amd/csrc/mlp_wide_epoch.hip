@@ -38,14 +38,6 @@
 // to fp32 tolerance against the per-minibatch path and the reference (tests/test_gpu_trainer.py).
 #include "common.h"
 
-// RAI_WE_NO_DEFER (A/B builds only): the W2 Adam at the end of its own step instead of in the next
-// step's A wait
-#ifdef RAI_WE_NO_DEFER
-constexpr bool WE_DEFER_W2 = false;
-#else
-constexpr bool WE_DEFER_W2 = true;
-#endif
-
 namespace {
 
 constexpr int WE_NT = 256;                  // threads per workgroup (4 waves)
@@ -811,10 +803,9 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
     we_arrive(ctr, WE_CA + net);
     if (w == 1) side_a();
     // (half of it: the other half runs under the H1 gather's LDS-DMA below)
-    if (WE_DEFER_W2 && mb > 0) adam_w2(0, 2);
+    if (mb > 0) adam_w2(0, 2);
     WSTAMP(22);  // (stamps: the A wait split into the deferred Adam and the rest of the wait)
     if (!we_wait(ctr, WE_CA + net, want, a.state, S.bail)) break;
-#ifndef RAI_WE_NO_XCC_LOCAL
     if (mb == 0) {  // every workgroup of the network registered its XCC before its step-0 A arrival
       if (tid == 0) {
         const unsigned long long m = __hip_atomic_fetch_or(&ctr[WE_CXCC * (WE_CTR_STRIDE / 8) + net], 0ull,
@@ -824,12 +815,11 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
       __syncthreads();
       xl = __builtin_amdgcn_readfirstlane(S.xl) != 0;
     }
-#endif
     WSTAMP(1);
     // H1 -> Act by LDS-DMA, and while it lands the deferred W2 Adam's other half (LDS rows W2r, disjoint
     // from Act); then the drain and the barrier
     we_gather_lds(a.ws, WE_H1_OFF + (int64_t)(net * 2 + par) * WE_ACT_SLOT, H, S.Act, w, lane, false);
-    if (WE_DEFER_W2 && mb > 0) adam_w2(2, 4);
+    if (mb > 0) adam_w2(2, 4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     // W2 rows j (as updated by the last Adam step, every wave's tiles: after the barrier) for this step's
@@ -888,24 +878,6 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
         qb[u] = O > 4 ? __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)off + 16, 0, WE_SC1))
                       : f4{0.f, 0.f, 0.f, 0.f};
       }
-#ifdef RAI_WE_W2T_EARLY  // A/B: the W2 column tiles issued before the partials land
-      // after the partials landed (in-order vmcnt: issued earlier, they would delay them): W2's column
-      // slice j (16 tiles of 1 KB, one LDS-DMA load each; needed at dH1, drained by the
-      // dZ2 gather's vmcnt).  Lane l lands at LDS slot (u = l >> 2, s = l & 3) and fetches piece
-      // we_w2t_slot(u, s) of row u (the swizzle is an involution: pre-swizzled source, as LDS-DMA needs)
-      {
-        const int u = lane >> 2;
-        const unsigned char* src =
-            a.ws + WE_W2T_OFF + net * WE_W2T_NET + (int64_t)j * 1024 + (u * WE_SL + 4 * we_w2t_slot(u, lane & 3)) * 4;
-#pragma unroll
-        for (int m = 0; m < WE_GMAX / 4; ++m) {
-          const int p = w + 4 * m;
-          if (p < G)
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(src + (int64_t)p * WE_GMAX * 1024),
-                                             &S.W2cT[p][0][0], 16, 0, WE_SC1);
-        }
-      }
-#endif
       f4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -915,7 +887,6 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
         }
       *reinterpret_cast<f4*>(&S.Pw[w][lane][0]) = sa;
       *reinterpret_cast<f4*>(&S.Pw[w][lane][4]) = sb;
-#ifndef RAI_WE_W2T_EARLY
       // after the partials landed (in-order vmcnt: issued earlier, they would delay them): W2's column
       // slice j (16 tiles of 1 KB, one LDS-DMA load each; needed at dH1, drained by the
       // dZ2 gather's vmcnt).  Lane l lands at LDS slot (u = l >> 2, s = l & 3) and fetches piece
@@ -932,11 +903,9 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
                                              &S.W2cT[p][0][0], 16, 0, WE_SC1);
         }
       }
-#endif
     }
     lds_barrier();
     WSTAMP(6);
-#ifndef RAI_WE_LOSS_ONE_WAVE
     if (HEAD == 1 && net == 0) {
       // Gaussian actor: every wave, 16 rows each, four lanes per row (lane & 3 = dimension pair dp: dims
       // 2 dp, 2 dp + 1).  The log-prob's eight per-dimension terms are gathered across the quad and summed
@@ -1012,9 +981,7 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
         S.st[3][r] = valid ? (double)ent : 0.0;
       }
       WSTAMP(7);
-    } else
-#endif
-    if (w == 0) {
+    } else if (w == 0) {
       const int r = lane;
       const bool valid = r < rows;
       const f4* lin = reinterpret_cast<const f4*>(&S.Xl[WE_B * WE_INMAX + r * WE_LIN]);
@@ -1463,9 +1430,7 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
       if (lane == 0) S.coef = coef;
       if (net == 0 && j == 0 && lane == 0 && a.norms && norm0 + mb < a.max_norms) a.norms[norm0 + mb] = total_norm;
     } else if (w == 1) {
-#ifndef RAI_WE_SKIP_SIDE_D  // timing experiments only: stale Adam constants and no stats rows
       side_d();
-#endif
     }
     __syncthreads();
     if (S.bail) break;
@@ -1474,7 +1439,6 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
       const float coef = S.coef;
       const float inv_c3 = S.adamc[0], c4 = S.adamc[1];
       // (the W2 row slice: deferred to the next step's A wait, adam_w2)
-      if (!WE_DEFER_W2) adam_w2(0, 4);
       if (WE_SL * w + li < IN) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1493,7 +1457,7 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
     lds_barrier();
     WSTAMP(21);
   }
-  if (WE_DEFER_W2 && !S.bail && nmb > 0) {  // the last step's deferred W2 Adam
+  if (!S.bail && nmb > 0) {  // the last step's deferred W2 Adam
     adam_w2(0, 4);
     lds_barrier();
   }

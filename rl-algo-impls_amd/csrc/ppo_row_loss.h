@@ -1,6 +1,6 @@
-// The per-row PPO loss and its gradient, shared by every 64-wide fused epoch kernel (mlp_net, mlp_rows,
-// mlp_mc, mlp_mc8).  Included once, inside mlp_ppo.hip's anonymous namespace, before any kernel body;
-// compiled under that file's fp contract(off).
+// The per-row PPO loss and its gradient, shared by every 64-wide fused epoch kernel (mlp_net, mlp_mc,
+// mlp_mc8).  Included once, inside mlp_ppo.hip's anonymous namespace, before any kernel body; compiled
+// under that file's fp contract(off).
 
 constexpr float F32_MIN = -3.4028234663852886e38f;
 

@@ -475,7 +475,6 @@ def _random_rollout(T, N, d, n, seed):
     (4, 2, "relu", 200, 9, 100, "mc4"),
     (2, 2, "tanh", 128, 5, 78, "mc"),        # in_dim 2 (padding columns), ragged tail (390 % 128 = 6)
     (3, 1, "tanh", 96, 6, 50, "mc"),         # one action
-    (4, 2, "tanh", 256, 8, 96, "rows"),      # diagnostic one-CU row-tile layout
     (4, 2, "tanh", 256, 8, 96, "chunk"),     # chunked one-CU layout
     (6, 3, "tanh", 128, 8, 64, "chunk"),     # Acrobot-like: generic (8, 8) instantiation
     (8, 8, "relu", 256, 4, 200, "chunk"),    # maximum shape of the chunked kernel
@@ -484,7 +483,6 @@ def _random_rollout(T, N, d, n, seed):
     (4, 2, "tanh", 40, 5, 50, "mc+vclip"),
     (4, 2, "tanh", 40, 5, 50, "mc8+vclip"),
     (4, 2, "tanh", 40, 5, 50, "mc4+vclip"),
-    (4, 2, "tanh", 40, 5, 50, "rows+vclip"),
     (4, 2, "tanh", 40, 5, 50, "chunk+vclip"),
     (6, 3, "tanh", 128, 8, 64, "chunk+vclip"),
 ])

@@ -1,6 +1,7 @@
 """Diagnostic: CartPole-v1 learning curve of the fused path per kernel layout and seed
-(RAI_MLP_LAYOUT).  Prints the first step count at which the rolling mean of the last 100
-episode returns passes 475, or the best mean reached in 100k steps.  Not part of the tests."""
+(RAI_MLP_LAYOUT: unset = the multi-CU default, chunk, mc4).  Prints the first step count at which
+the rolling mean of the last 100 episode returns passes 475, or the best mean reached in 100k
+steps.  Not part of the tests."""
 import os
 import sys
 from pathlib import Path

@@ -8,7 +8,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-# RAI_STAMPS_LIB: another stamps build (e.g. build.py alt with RAI_ALT_FLAGS="-DRAI_STAMPS -DRAI_M8_LDS_DW2")
+# RAI_STAMPS_LIB: another stamps build (e.g. build.py alt with RAI_ALT_FLAGS="-DRAI_STAMPS" plus an A/B flag)
 os.environ["RAI_AMD_LIB"] = os.environ.get("RAI_STAMPS_LIB",
                                            str(ROOT / "rl-algo-impls_amd" / "lib" / "librai_amd_stamps.so"))
 import numpy as np  # noqa: E402
@@ -31,9 +31,6 @@ NAMES = {
             "share sum + round 2 publish + wait", "all-gather + norm + adam + barrier"],
     "mc4": ["F1+F2 forward", "out layer + loss + dZ2", "dH1 + partials + barrier", "P_B dW2 + sums",
            "publish + counter wait", "reduce G slots + |g|^2", "stats + norm exchange", "adam"],
-    "rows": ["F1 layer1 (wave-local)", "F2 layer2 + epilogue", "out layer + loss + dZ2", "dH1 MFMA",
-             "dZ1/partials + barrier", "P_B dW2 MFMA", "E2 owner sums + norm", "E3 stats + exchange",
-             "E4 adam"],
 }[LAYOUT]
 dev = torch.device("cuda", 0)
 torch.manual_seed(1)
