@@ -22,16 +22,13 @@
 // published, i.e. finished reading the previous parity).  Every spin is bounded and sets the
 // state's err flag instead of hanging.  The 8 workgroups are placed by blockIdx on two XCDs
 // (blocks b with b % 8 in {0, 1}; round-robin dispatch), a locality bonus, never a correctness
-// requirement.
+// requirement.  One GPU only: across GPUs this kernel is the grads / apply step of the per-step loop
+// (rai_mlp_ppo_dp_step); the in-kernel cross-GPU exchange is mlp_mc8.h's.
 
 constexpr int MC_G = 4;              // CUs per network
-constexpr int MC_NT = 256;           // threads per CU (4 waves, one per SIMD)
-constexpr int MC_NW = MC_NT / 64;
 constexpr int MC_RC = 64;            // minibatch rows per CU (MC_NW 16-row tiles)
 constexpr int MC_GRID = 8 * MC_G;    // blocks launched; only b % 8 < 2 work
 constexpr int MC_SLOT = WL_N;        // floats per exchange slot (one partial gradient)
-static_assert(MC_CPT * MC_NT >= WL_CH, "chunks per thread");
-static_assert(2 * XDP_MAXW * MC_G * 8 <= XDP_TEST_OFF, "xdp flags");
 
 // sync words (u64) at the start of the workspace, zeroed before every launch
 constexpr int MC_CNT = 0;     // [2 nets] arrival counters
@@ -89,46 +86,13 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
   const int szA = HID * IN + HID + HID * HID + HID + NA * HID + NA;
   const int base = net == 0 ? 0 : szA;
 
-  // ---- weights -> LDS (weight layout); partial-gradient buffer zeroed (padding stays 0) -------
-  {
-    // fully unrolled so all ~19 loads per thread are in flight at once (a rolled loop waits for
-    // each load before the next: ~19 memory latencies, paid on every data-parallel launch)
-    constexpr int NE = (WL_N + MC_NT - 1) / MC_NT;
-    float wv[NE];
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const int e = tid + MC_NT * i;
-      const int f = e < WL_N ? wl_to_flat<OUTP>(e, IN, OUT, base) : -1;
-      wv[i] = ld_or0(a.params, f);
-    }
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const int e = tid + MC_NT * i;
-      if (e < WL_N) {
-        S.Wt[e] = wv[i];
-        S.Gb[e] = 0.f;
-      }
-    }
-  }
-  // ---- Adam moments of the owned chunks (chunk ch = tid + MC_NT * i), in registers -----------
+  mc_load_weights<OUTP>(a, S.Wt, S.Gb, tid, IN, OUT, base);
 #ifdef RAI_STAMPS
   const unsigned long long t_w = __builtin_amdgcn_s_memtime();
 #endif
-  f4 mreg[MC_CPT], vreg[MC_CPT];
-#pragma unroll
-  for (int i = 0; i < MC_CPT; ++i) {
-    mreg[i] = f4{0.f, 0.f, 0.f, 0.f};
-    vreg[i] = f4{0.f, 0.f, 0.f, 0.f};
-    const int ch = tid + MC_NT * i;
-    if (!grads_mode || apply_in) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int f = ch < WL_CH ? wl_to_flat<OUTP>(4 * ch + q, IN, OUT, base) : -1;
-        mreg[i][q] = ld_or0(a.exp_avg, f);
-        vreg[i][q] = ld_or0(a.exp_avg_sq, f);
-      }
-    }
-  }
+  // grads mode without a gradient to apply carries no optimizer state (exp_avg / exp_avg_sq are null)
+  f4 mreg[MC_CPT] = {}, vreg[MC_CPT] = {};
+  if (!grads_mode || apply_in) mc_load_moments<OUTP>(a, mreg, vreg, tid, IN, OUT, base);
 
 #ifdef RAI_STAMPS
   const unsigned long long t_mv = __builtin_amdgcn_s_memtime();
@@ -208,8 +172,7 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
     double tot = 0.0;
     for (int q = 0; q < MC_NW; ++q) tot += S.red[q];
     const float total_norm = (float)sqrt(tot);
-    float coef = 1.f;
-    if (max_grad_norm > 0.f) coef = fminf(max_grad_norm / (total_norm + 1e-6f), 1.f);
+    const float coef = clip_coef(max_grad_norm, total_norm);
     const double bc1 = 1.0 - ipow(beta1_d, step0 + 1);
     const double bc2 = 1.0 - ipow(beta2_d, step0 + 1);
     const float inv_bc2_sqrt = 1.f / (float)sqrt(bc2), neg_step = (float)(-((double)lr / bc1));
@@ -262,10 +225,9 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
   __syncthreads();
 
   // Bounded waits, by elapsed s_memrealtime ticks (the constant 100 MHz counter, common.h
-  // rai_clock): 2 s for partners on this GPU (they are co-resident and a minibatch apart at most),
-  // 60 s for other GPUs (their ranks can start an epoch later by host-side jitter: rollouts,
-  // collectives).  A timeout sets err and stops the CU.
-  constexpr long long MC_WAIT_LOCAL = RAI_SPIN_LOCAL, MC_WAIT_REMOTE = RAI_SPIN_REMOTE;
+  // rai_clock): 2 s for partners on this GPU (they are co-resident and a minibatch apart at most).
+  // A timeout sets err and stops the CU.
+  constexpr long long MC_WAIT_LOCAL = RAI_SPIN_LOCAL;
   for (int mb = mb_begin; mb < mb_end; ++mb) {
     const int kk_mb = mb - mb_begin;
     const int par = mb & 1;
@@ -521,11 +483,7 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
         for (int q = 0; q < MC_NW; ++q)
 #pragma unroll
           for (int i = 0; i < 4; ++i) sv[i] += S.st[q][i];
-        const u4v p0 = __builtin_bit_cast(u4v, (double __attribute__((ext_vector_type(2)))){sv[0], sv[1]});
-        const u4v p1 = __builtin_bit_cast(u4v, (double __attribute__((ext_vector_type(2)))){sv[2], sv[3]});
-        const int so = ((net * nmb + kk_mb) * MC_G + c) * 32;
-        __builtin_amdgcn_raw_buffer_store_b128(p0, str, so, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(p1, str, so + 16, 0, 16);
+        mc_statp_store<MC_G>(str, net, nmb, kk_mb, c, sv);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY storing wave drains its stores
     }
@@ -567,60 +525,6 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
 #pragma unroll
           for (int cc = 1; cc < MC_G; ++cc) sum += v[i][cc];
           gr[i] = sum;
-        }
-      }
-      if (a.xworld > 1) {
-        // ---- cross-GPU sum over xGMI peer memory: CU c pushes its 1/G share of this rank's
-        // gradient into every rank's region (system-scope 16-B stores), drains, then stamps one
-        // flag per receiver; each CU waits for all world*G flags of this step in its own region
-        // and sums the world slots in rank order (identical bits on every rank). ------------------
-        const int W = a.xworld;
-        const unsigned long long step_id = (unsigned long long)(a.xbase + kk_mb + 1);
-        const int xpar = (int)((a.xbase + kk_mb) & 1);  // global-step parity: mb restarts at 0 every launch
-        const int slot_off = XDP_FLAGS_BYTES + ((xpar * W + a.xrank) * 2 + net) * WL_N * (int)sizeof(float);
-        for (int pr = 0; pr < W; ++pr) {
-          const __amdgpu_buffer_rsrc_t prs = mc_rsrc(a.xpeers[pr], (int)xdp_region_bytes(W));
-#pragma unroll
-          for (int i = 0; i < MC_CPT; ++i) {
-            const int ch = tid + MC_NT * i;
-            if (ch < WL_CH && ch % MC_G == c)
-              __builtin_amdgcn_raw_buffer_store_b128(as_u4(gr[i]), prs, slot_off + 16 * ch, 0, XDP_AUX);
-          }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: shares landed
-        __syncthreads();
-        if (tid < W) {  // one flag store per receiver, after the whole workgroup drained
-          unsigned long long* fl = reinterpret_cast<unsigned long long*>(a.xpeers[tid]) +
-                                   (net * XDP_MAXW + a.xrank) * MC_G + c;
-          __hip_atomic_store(fl, step_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        if (w == 0) {  // one wave polls this rank's W*G flags of this network
-          const unsigned long long* fl = reinterpret_cast<const unsigned long long*>(a.xpeers[a.xrank]) +
-                                         net * XDP_MAXW * MC_G;
-          const unsigned long long t0 = rai_clock();
-          for (;;) {
-            bool ok = true;
-            if (lane < W * MC_G)
-              ok = __hip_atomic_load(fl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= step_id;
-            if (__all(ok)) break;
-            if (rai_expired(t0, MC_WAIT_REMOTE)) {
-              if (lane == 0) { atomicExch(a.err, 1); S.bail = 1; }
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
-        }
-        __syncthreads();
-        const __amdgpu_buffer_rsrc_t lrs = mc_rsrc(a.xpeers[a.xrank], (int)xdp_region_bytes(W));
-#pragma unroll
-        for (int i = 0; i < MC_CPT; ++i) {
-          const int chl = min(tid + MC_NT * i, WL_CH - 1);
-          f4 sum = f4{0.f, 0.f, 0.f, 0.f};
-          for (int pr = 0; pr < W; ++pr) {
-            const int off = XDP_FLAGS_BYTES + ((xpar * W + pr) * 2 + net) * WL_N * (int)sizeof(float);
-            sum += as_f4(__builtin_amdgcn_raw_buffer_load_b128(lrs, off + 16 * chl, 0, XDP_AUX));
-          }
-          if (tid + MC_NT * i < WL_CH) gr[i] = sum;
         }
       }
 #pragma unroll
@@ -680,8 +584,7 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
     if (grads_mode) continue;
     {
       const float total_norm = (float)sqrt((double)S.bcast[0] + (double)S.bcast[1]);
-      float coef = 1.f;
-      if (max_grad_norm > 0.f) coef = fminf(max_grad_norm / (total_norm + 1e-6f), 1.f);
+      const float coef = clip_coef(max_grad_norm, total_norm);
       const float inv_bc2_sqrt = 1.f / S.bcast[2], neg_step = S.bcast[3];
       const float w1 = (float)(1.0 - beta1_d), w2 = (float)(1.0 - beta2_d);
       RELANE();
@@ -709,59 +612,18 @@ __device__ __forceinline__ void mlp_mc(const MlpArgs& a, SmemM<OUTP>& S, const i
 
   STAMP(12);
   // ---- stats rows of every minibatch (CU 0): sum the CUs' partials in CU order ---------------------
-  // (every CU published minibatch k's partial before the counter wait CU 0 passed for k)
   if (c == 0 && !S.bail && a.stats) {
     for (int k = tid; k < nmb; k += MC_NT) {
       const int srow = stat0 + k;
       if (srow >= a.max_stats) continue;
       const int64_t r0 = (int64_t)(mb_begin + k) * B;
       const int rws = (int)min((int64_t)B, n_rows - r0);
-      double sv[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int cc = 0; cc < MC_G; ++cc) {
-        const int so = ((net * nmb + k) * MC_G + cc) * 32;
-        const auto d0 = __builtin_bit_cast(double __attribute__((ext_vector_type(2))),
-                                           __builtin_amdgcn_raw_buffer_load_b128(str, so, 0, 16));
-        const auto d1 = __builtin_bit_cast(double __attribute__((ext_vector_type(2))),
-                                           __builtin_amdgcn_raw_buffer_load_b128(str, so + 16, 0, 16));
-        sv[0] += d0[0];
-        sv[1] += d0[1];
-        sv[2] += d1[0];
-        sv[3] += d1[1];
-      }
-      float* row = a.stats + (int64_t)srow * RAI_STAT_STRIDE;
-      const double Bd = (double)rws * (double)a.world;
-      if (ACTOR) {
-        const float pi_loss = (float)(-sv[0] / Bd);
-        const float ent_loss = (float)(-sv[3] / Bd);
-        row[0] = lh.pi_coef * pi_loss + lh.ent_coef * ent_loss;  // host adds the value term
-        row[1] = pi_loss;
-        row[2] = ent_loss;
-        row[3] = (float)(sv[1] / Bd);
-        row[4] = (float)(sv[2] / Bd);
-      } else {
-        row[5] = (float)(sv[0] / Bd) * lh.halve;
-        row[5 + RAI_MAX_K] = lh.has_vclip ? (float)(sv[1] / Bd) : 0.f;
-      }
+      double sv[4];
+      mc_statp_sum<MC_G>(str, net, nmb, k, sv);
+      stat_row_write<ACTOR>(a.stats + (int64_t)srow * RAI_STAT_STRIDE, sv, rws, a.world, lh);
     }
   }
-  // ---- write back parameters and optimizer moments -----------------------------------------------
-  if ((!grads_mode || apply_in) && !S.bail) {  // identical copies on every CU: each writes 1/G
-#pragma unroll
-    for (int i = 0; i < MC_CPT; ++i) {
-      const int ch = tid + MC_NT * i;
-      if (ch < WL_CH && ch % MC_G == c) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int f = wl_to_flat<OUTP>(4 * ch + q, IN, OUT, base);
-          if (f >= 0) {
-            a.params[f] = S.Wt[4 * ch + q];
-            a.exp_avg[f] = mreg[i][q];
-            a.exp_avg_sq[f] = vreg[i][q];
-          }
-        }
-      }
-    }
-  }
+  if ((!grads_mode || apply_in) && !S.bail) mc_write_back<OUTP, MC_G>(a, S.Wt, mreg, vreg, tid, c, IN, OUT, base);
   STAMP(13);
 #ifdef RAI_STAMPS
   if (c == 0 && tid < 32) atomicAdd(&g_stamps[net][tid], S.stamps[tid]);  // summed over launches

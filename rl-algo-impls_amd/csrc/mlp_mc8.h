@@ -53,8 +53,6 @@
 // unaffected.  Every spin is bounded by elapsed clock and sets state.err.
 
 constexpr int M8_GMAX = 16;                          // largest CUs-per-network instantiation
-constexpr int M8_NT = 256;                           // threads per CU (4 waves)
-constexpr int M8_NW = M8_NT / 64;
 // Geometry for G CUs per network: RC rows per CU in NTILE 16-row tiles, WPT waves per tile, each
 // wave owning CT 16-column tiles of the hidden layers; SH float4 chunks per gradient share.  RC defaults
 // to MAXB / G (a 256-row minibatch over all G CUs); the per-rank geometry of data parallel keeps RC = 16
@@ -64,12 +62,12 @@ template <int G, int RCV = MAXB / G>
 struct M8Geo {
   static constexpr int RC = RCV;
   static constexpr int NTILE = RC / 16;
-  static constexpr int WPT = M8_NW / NTILE;
+  static constexpr int WPT = MC_NW / NTILE;
   static constexpr int CT = HID / 16 / WPT;
   static constexpr int SH = (WL_CH + G - 1) / G;
   static constexpr int GRID = 8 * G;                 // blocks launched; only b % 8 < 2 work
-  static_assert(RC % 16 == 0 && NTILE * WPT == M8_NW && CT * WPT * 16 == HID, "geometry");
-  static_assert(SH <= M8_NT, "one share chunk per thread");
+  static_assert(RC % 16 == 0 && NTILE * WPT == MC_NW && CT * WPT * 16 == HID, "geometry");
+  static_assert(SH <= MC_NT, "one share chunk per thread");
 };
 // sync words (u64, zeroed per launch): round-1 and round-2 arrival counters per network; per network
 // the set of XCCs its CUs run on (one bit per HW_REG_XCC_ID)
@@ -83,9 +81,8 @@ constexpr int M8_BC_MAX = 2048;
 constexpr int64_t M8_S1_BYTES = 2LL * 2 * M8_GMAX * WL_N * sizeof(float);  // [net][par][c][WL_N] partials
 constexpr int64_t M8_S2_OFF = M8_S1_BYTES;                                  // [net][par][WL_N] summed gradient
 constexpr int64_t M8_SQ_OFF = M8_S2_OFF + 2LL * 2 * WL_N * sizeof(float);   // [par][net][c][hi, lo] share |g|^2 granules
-constexpr int64_t M8_SCRATCH = M8_SQ_OFF + 2LL * 2 * M8_GMAX * M8_NW * sizeof(double);
+constexpr int64_t M8_SCRATCH = M8_SQ_OFF + 2LL * 2 * M8_GMAX * MC_NW * sizeof(double);
 static_assert(2 * XDP_MAXW * M8_GMAX * 8 <= XDP_TEST_OFF, "xdp share flags");
-static_assert(MC_CPT * M8_NT >= WL_CH, "chunks per thread");
 
 template <int OUTP, int G, int RCV>
 struct SmemM8 {
@@ -94,7 +91,7 @@ struct SmemM8 {
   unsigned long long stamps[32];
   unsigned long long t_last;
 #endif
-  double sq[M8_NW];  // round 2: the wave parts of this CU's share |g|^2
+  double sq[MC_NW];  // round 2: the wave parts of this CU's share |g|^2
   float strow[Geo::RC][4];  // per-row loss statistics, reduced off the critical path (round-1 wait)
   int bail;
   int xl;            // every CU of this network on one XCC: gradient slots published with plain stores
@@ -172,29 +169,33 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
   const int szA = HID * IN + HID + HID * HID + HID + NA * HID + NA;
   const int base = net == 0 ? 0 : szA;
 
+  // Four phases below are spelled out here although mlp_mc_common.h has them as helpers (mc_load_weights,
+  // mc_load_moments, mc_statp_sum + stat_row_write, mc_write_back; mlp_mc.h calls those): called from this
+  // kernel, each of them changes its register allocation and instruction schedule, and the default kernel's
+  // device code is kept as measured.  A change to one of them goes to both places.
   // ---- weights -> LDS (weight layout); partial-gradient buffer zeroed (padding stays 0) -------
   {
-    constexpr int NE = (WL_N + M8_NT - 1) / M8_NT;
+    constexpr int NE = (WL_N + MC_NT - 1) / MC_NT;
     float wv[NE];
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
-      const int e = tid + M8_NT * i;
+      const int e = tid + MC_NT * i;
       wv[i] = ld_or0(a.params, e < WL_N ? wl_to_flat<OUTP>(e, IN, OUT, base) : -1);
     }
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
-      const int e = tid + M8_NT * i;
+      const int e = tid + MC_NT * i;
       if (e < WL_N) {
         S.Wt[e] = wv[i];
         S.Gb[e] = 0.f;
       }
     }
   }
-  // ---- Adam moments of chunks ch = tid + M8_NT * i (every CU updates the whole network) -------
+  // ---- Adam moments of chunks ch = tid + MC_NT * i (every CU updates the whole network) -------
   f4 mreg[MC_CPT], vreg[MC_CPT];
 #pragma unroll
   for (int i = 0; i < MC_CPT; ++i) {
-    const int ch = tid + M8_NT * i;
+    const int ch = tid + MC_NT * i;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int f = ch < WL_CH ? wl_to_flat<OUTP>(4 * ch + q, IN, OUT, base) : -1;
@@ -269,7 +270,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
     inv_bc2_sqrt = 1.f / (float)sqrt(1.0 - ipow(beta2_d, t));
     neg_step = (float)(-((double)lr / (1.0 - ipow(beta1_d, t))));
   };
-  for (int k = tid; k < min(nmb, M8_BC_MAX); k += M8_NT) bias_corr(k, S.bc[k][0], S.bc[k][1]);
+  for (int k = tid; k < min(nmb, M8_BC_MAX); k += MC_NT) bias_corr(k, S.bc[k][0], S.bc[k][1]);
   if (tid == 0) {
     S.bail = 0;
     S.xl = 0;
@@ -614,7 +615,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
         for (int q = 1; q < NTILE; ++q) v += S.Ps[q][p][j];
         return v;
       };
-      for (int e = tid; e < HID * 4 + 2 * HID + OUTP * HID + OUTP; e += M8_NT) {
+      for (int e = tid; e < HID * 4 + 2 * HID + OUTP * HID + OUTP; e += MC_NT) {
         float sum;
         int dst;
         if (e < HID * 4) {  // W1[j][k]
@@ -655,7 +656,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       // b2, W3, b3 and the tail padding), at most one per thread
       RELANE();
       constexpr int C0 = WL_W2 / 4, C1 = WL_B2 / 4, NS = C0 + WL_CH - C1;
-      static_assert(NS <= M8_NT, "one small-tensor chunk per thread");
+      static_assert(NS <= MC_NT, "one small-tensor chunk per thread");
       const int sbase = ((net * 2 + par) * G + c) * WL_N * (int)sizeof(float);
       const int ch = min(tid < C0 ? tid : tid + (C1 - C0), WL_CH - 1);
       const f4 pv = *reinterpret_cast<const f4*>(&S.Gb[4 * ch]);
@@ -670,17 +671,17 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       const int sbase = ((net * 2 + par) * G + c) * WL_N * (int)sizeof(float);
       f4 pv[MC_CPT];
 #pragma unroll
-      for (int i = 0; i < MC_CPT; ++i) pv[i] = *reinterpret_cast<const f4*>(&S.Gb[4 * min(tid + M8_NT * i, WL_CH - 1)]);
+      for (int i = 0; i < MC_CPT; ++i) pv[i] = *reinterpret_cast<const f4*>(&S.Gb[4 * min(tid + MC_NT * i, WL_CH - 1)]);
       if (__builtin_amdgcn_readfirstlane(S.xl)) {  // one XCC: plain stores, the lines stay in its L2
 #pragma unroll
         for (int i = 0; i < MC_CPT; ++i) {
-          const int ch = tid + M8_NT * i;
+          const int ch = tid + MC_NT * i;
           if (ch < WL_CH) __builtin_amdgcn_raw_buffer_store_b128(as_u4(pv[i]), srs, sbase + 16 * ch, 0, 0);
         }
       } else {
 #pragma unroll
         for (int i = 0; i < MC_CPT; ++i) {
-          const int ch = tid + M8_NT * i;
+          const int ch = tid + MC_NT * i;
           if (ch < WL_CH) __builtin_amdgcn_raw_buffer_store_b128(as_u4(pv[i]), srs, sbase + 16 * ch, 0, 16);
         }
       }
@@ -710,13 +711,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       double sv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) sv[i] = wave_sum_v(ln < RC ? (double)S.strow[ln < RC ? ln : 0][i] : 0.0);
-      if (ln == 0) {
-        const u4v p0 = __builtin_bit_cast(u4v, (double __attribute__((ext_vector_type(2)))){sv[0], sv[1]});
-        const u4v p1 = __builtin_bit_cast(u4v, (double __attribute__((ext_vector_type(2)))){sv[2], sv[3]});
-        const int so = ((net * nmb + mb) * G + c) * 32;
-        __builtin_amdgcn_raw_buffer_store_b128(p0, str, so, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(p1, str, so + 16, 0, 16);
-      }
+      if (ln == 0) mc_statp_store<G>(str, net, nmb, mb, c, sv);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else if (w == 3 && mb + 1 < nmb) {
       pf_issue(mb + 1);  // the next step's rows: loads in flight through round 2
@@ -762,21 +757,18 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
         const int W = a.xworld;
         const unsigned long long step_id = (unsigned long long)(a.xbase + mb + 1);
         const int xpar = (int)((a.xbase + mb) & 1);  // global-step parity: mb restarts at 0 every launch
-        const int slot_off = XDP_FLAGS_BYTES + ((xpar * W + a.xrank) * 2 + net) * WL_N * (int)sizeof(float);
+        const int slot_off = xdp_slot_off(xpar, W, a.xrank, net);
         for (int pr = 0; pr < W; ++pr) {
           const __amdgpu_buffer_rsrc_t prs = mc_rsrc(a.xpeers[pr], (int)xdp_region_bytes(W));
           if (own) __builtin_amdgcn_raw_buffer_store_b128(as_u4(s), prs, slot_off + 16 * ch, 0, XDP_AUX);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid < W) {
-          unsigned long long* fl = reinterpret_cast<unsigned long long*>(a.xpeers[tid]) +
-                                   (net * XDP_MAXW + a.xrank) * G + c;
-          __hip_atomic_store(fl, step_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (tid < W)
+          __hip_atomic_store(xdp_flag(a.xpeers[tid], net, a.xrank, G, c), step_id, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
         if (w == 0) {
-          const unsigned long long* fl = reinterpret_cast<const unsigned long long*>(a.xpeers[a.xrank]) +
-                                         (net * XDP_MAXW + lane) * G + c;
+          const unsigned long long* fl = xdp_flag(a.xpeers[a.xrank], net, lane, G, c);
           const unsigned long long t0 = rai_clock();
           for (;;) {
             bool ok = true;
@@ -792,10 +784,8 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
         __syncthreads();
         const __amdgpu_buffer_rsrc_t lrs = mc_rsrc(a.xpeers[a.xrank], (int)xdp_region_bytes(W));
         f4 sum = f4{0.f, 0.f, 0.f, 0.f};
-        for (int pr = 0; pr < W; ++pr) {
-          const int off = XDP_FLAGS_BYTES + ((xpar * W + pr) * 2 + net) * WL_N * (int)sizeof(float);
-          sum += as_f4(__builtin_amdgcn_raw_buffer_load_b128(lrs, off + 16 * chl, 0, XDP_AUX));
-        }
+        for (int pr = 0; pr < W; ++pr)
+          sum += as_f4(__builtin_amdgcn_raw_buffer_load_b128(lrs, xdp_slot_off(xpar, W, pr, net) + 16 * chl, 0, XDP_AUX));
         s = sum;
       }
       STAMP(11);
@@ -853,12 +843,12 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       const int gbase = (int)M8_S2_OFF + (net * 2 + par) * WL_N * (int)sizeof(float);
 #pragma unroll
       for (int i = 0; i < MC_CPT; ++i) {
-        const int chl = min(tid + M8_NT * i, WL_CH - 1);
+        const int chl = min(tid + MC_NT * i, WL_CH - 1);
         gr[i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srs, gbase + 16 * chl, 0, 16));
       }
       // the 2G share norms (net-major, CU order), lane l polling the granules of number l until both
       // carry this step's tag (they were stored before their CU's round-2 arrival); fixed-order wave sum
-      static_assert(M8_NW == 4, "four wave parts per share norm");
+      static_assert(MC_NW == 4, "four wave parts per share norm");
       const unsigned long long* gq = sq_gran + (par * 2 * G + min(lane, 2 * G - 1)) * 2;
       const unsigned tag = (unsigned)(step0 + mb + 1);
       unsigned long long qh, ql;
@@ -881,13 +871,12 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       const double tot = wave_sum_v(lane < 2 * G ? sq : 0.0);
       const float total_norm = (float)sqrt(tot);
       STAMP(14);
-      float coef = 1.f;
-      if (max_grad_norm > 0.f) coef = fminf(max_grad_norm / (total_norm + 1e-6f), 1.f);
+      const float coef = clip_coef(max_grad_norm, total_norm);
       // branch-free over the chunks (one basic block: the transcendentals of all chunks interleave); a lane
       // past the last chunk updates a clamped copy and stores nothing (its moments are never written back)
 #pragma unroll
       for (int i = 0; i < MC_CPT; ++i) {
-        const int ch = tid + M8_NT * i;
+        const int ch = tid + MC_NT * i;
         {
           f4 p = *reinterpret_cast<const f4*>(&S.Wt[4 * min(ch, WL_CH - 1)]);
           const f2a C2 = {coef, coef};
@@ -915,7 +904,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
 
   // ---- stats rows of every minibatch (CU 0): sum the CUs' partials in CU order ---------------------
   if (c == 0 && !S.bail && a.stats) {
-    for (int k = tid; k < nmb; k += M8_NT) {
+    for (int k = tid; k < nmb; k += MC_NT) {
       const int srow = stat0 + k;
       if (srow >= a.max_stats) continue;
       const int64_t r0 = (int64_t)k * B;
@@ -952,7 +941,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
   if (!S.bail) {
 #pragma unroll
     for (int i = 0; i < MC_CPT; ++i) {
-      const int ch = tid + M8_NT * i;
+      const int ch = tid + MC_NT * i;
       if (ch < WL_CH && ch % G == c) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -979,7 +968,7 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
 }
 
 template <int RELU, int G, int RCV = MAXB / G>
-__global__ __launch_bounds__(M8_NT) void mlp_ppo_mc8_kernel(const MlpArgs a) {
+__global__ __launch_bounds__(MC_NT) void mlp_ppo_mc8_kernel(const MlpArgs a) {
   static_assert(sizeof(SmemM8<2, G, RCV>) <= 160 * 1024, "LDS budget");
   __shared__ __attribute__((aligned(16))) unsigned char smem_raw[sizeof(SmemM8<2, G, RCV>)];
   const int b = blockIdx.x, xcd = b & 7, c = b >> 3;
