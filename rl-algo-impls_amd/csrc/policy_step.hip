@@ -319,18 +319,18 @@ void launch_step(const StepArgs& a, int relu, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int rai_mlp_policy_step(const float* const* pi_params, const float* const* v_params, const float* obs,
-                                   int64_t N, int32_t in_dim, int32_t hidden, int32_t n_actions,
-                                   int32_t activation, uint64_t seed, uint64_t offset, int64_t* actions_out,
-                                   float* logp_out, float* values_out, void* stream) {
-  if (!v_params || !obs || !values_out) return RAI_E_NULLPTR;
-  if ((actions_out == nullptr) != (logp_out == nullptr) || (actions_out && !pi_params)) return RAI_E_NULLPTR;
+// What the two entry points share, after their own null checks (the caller has checked pi_params wherever
+// actions_out is set): the shape and activation checks, the per-layer pointer checks, the fields of `a` both
+// forms fill (a arrives holding the caller's extra fields, the rest zero), the instantiation choice, the launch.
+static int step_checked_launch(StepArgs a, const float* const* pi_params, const float* const* v_params,
+                               const float* obs, int64_t N, int32_t in_dim, int32_t hidden, int32_t n_actions,
+                               int32_t activation, uint64_t seed, uint64_t offset, int64_t* actions_out,
+                               float* logp_out, float* values_out, void* stream) {
   if (hidden != HID || in_dim < 1 || in_dim > 8 || n_actions < 1 || n_actions > 8 || N < 1 ||
       (activation != 0 && activation != 1))
     return RAI_E_SHAPE;
   for (int i = 0; i < 6; ++i)
     if (!v_params[i] || (actions_out && !pi_params[i])) return RAI_E_NULLPTR;
-  StepArgs a = {};
   if (actions_out) a.pi = {pi_params[0], pi_params[1], pi_params[2], pi_params[3], pi_params[4], pi_params[5]};
   a.v = {v_params[0], v_params[1], v_params[2], v_params[3], v_params[4], v_params[5]};
   a.obs = obs;
@@ -349,6 +349,16 @@ extern "C" int rai_mlp_policy_step(const float* const* pi_params, const float* c
   return RAI_OK;
 }
 
+extern "C" int rai_mlp_policy_step(const float* const* pi_params, const float* const* v_params, const float* obs,
+                                   int64_t N, int32_t in_dim, int32_t hidden, int32_t n_actions,
+                                   int32_t activation, uint64_t seed, uint64_t offset, int64_t* actions_out,
+                                   float* logp_out, float* values_out, void* stream) {
+  if (!v_params || !obs || !values_out) return RAI_E_NULLPTR;
+  if ((actions_out == nullptr) != (logp_out == nullptr) || (actions_out && !pi_params)) return RAI_E_NULLPTR;
+  return step_checked_launch(StepArgs{}, pi_params, v_params, obs, N, in_dim, hidden, n_actions, activation, seed,
+                             offset, actions_out, logp_out, values_out, stream);
+}
+
 // The same step with the host hand-off folded in (the CartPole-class rollout loop,
 // rl_algo_impls/rollout/sync_step_rollout.py:193-207): the env's next observations, rewards and
 // terminations are read by the kernel straight from host-mapped pinned memory (rai_host_alloc) and
@@ -364,34 +374,15 @@ extern "C" int rai_mlp_policy_step_mapped(const float* const* pi_params, const f
   if (!v_params || !obs_slot || !values_out || !pi_params || !actions_out || !logp_out) return RAI_E_NULLPTR;
   if ((rew_host == nullptr) != (rew_dst == nullptr) || (done_host == nullptr) != (done_dst == nullptr))
     return RAI_E_NULLPTR;
-  if (hidden != HID || in_dim < 1 || in_dim > 8 || n_actions < 1 || n_actions > 8 || N < 1 ||
-      (activation != 0 && activation != 1))
-    return RAI_E_SHAPE;
-  for (int i = 0; i < 6; ++i)
-    if (!v_params[i] || !pi_params[i]) return RAI_E_NULLPTR;
   StepArgs a = {};
-  a.pi = {pi_params[0], pi_params[1], pi_params[2], pi_params[3], pi_params[4], pi_params[5]};
-  a.v = {v_params[0], v_params[1], v_params[2], v_params[3], v_params[4], v_params[5]};
-  a.obs = obs_slot;
-  a.N = N;
-  a.in_dim = in_dim;
-  a.n_act = n_actions;
-  a.seed = seed;
-  a.offset = offset;
-  a.actions = actions_out;
-  a.logp = logp_out;
-  a.values = values_out;
   a.obs_host = obs_host;
   a.rew_host = rew_host;
   a.rew_dst = rew_dst;
   a.done_host = done_host;
   a.done_dst = done_dst;
   a.act_host = actions_host;
-  hipStream_t s = rai_stream(stream);
-  if (in_dim <= 4 && n_actions <= 2) launch_step<4, 2>(a, activation, s);
-  else launch_step<8, 8>(a, activation, s);
-  RAI_LAUNCH_CHECK();
-  return RAI_OK;
+  return step_checked_launch(a, pi_params, v_params, obs_slot, N, in_dim, hidden, n_actions, activation, seed, offset,
+                             actions_out, logp_out, values_out, stream);
 }
 
 // Host-mapped pinned memory for the kernels above: coherent (fine-grained) host memory the GPU reads and

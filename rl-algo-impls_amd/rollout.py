@@ -462,6 +462,10 @@ class SyncStepRolloutGenerator(RolloutGenerator):
         if (spec is not None and self.discrete and self.get_action_mask is None
                 and self.obs_dtype == torch.float32 and len(obs_space.shape) == 1):
             self.fused_step = spec
+            assert self.action_masks is None and self.obs_dtype == torch.float32  # what the mapped loop relies on
+        # CartPole-class policies take the mapped loop (_mapped_step_loop); RAI_ROLLOUT_MAPPED=0 is a diagnostic
+        # that sends them through the generic loop, the independent form the bit-identity test compares against
+        self._mapped_loop = self.fused_step is not None and os.environ.get("RAI_ROLLOUT_MAPPED", "1") != "0"
         # wide-MLP policies (HalfCheetah class): the rollout forward as rai_mlp_wide_dist_params (3
         # launches) instead of the PyTorch module; RAI_ROLLOUT_WIDE=0 keeps the module
         self._wide_fwd = None
@@ -485,6 +489,25 @@ class SyncStepRolloutGenerator(RolloutGenerator):
             if self._sde_kernels:
                 self.sde_E = torch.zeros((N, H, A), dtype=torch.float32, device=dev)
                 self.sde_E0 = torch.zeros((H, A), dtype=torch.float32, device=dev)
+        # the generic loop's policy step and action source, fixed here.  The step is kept as a plain function
+        # of (self, s): a bound method stored on the instance would make it a reference cycle, and the buffers
+        # would wait for the cycle collector
+        cls, net = SyncStepRolloutGenerator, policy.network
+        if self.fused_step is not None:
+            self._step_fn = cls._fused_step
+        elif self.gridnet:
+            self._step_fn = cls._gridnet_step
+        elif self.sde is not None:
+            self._step_fn = cls._sde_step
+        else:
+            self._step_fn = cls._forward_sample_step
+            if self.multidiscrete:
+                self._fwd = net.md_logits_and_value
+            else:
+                self._fwd = self._wide_fwd if self._wide_fwd is not None else net.dist_params_and_value
+        # what the env receives at step s is _act_src[s]: the slot's actions, or the clamped Box actions at every
+        # s (a stride-0 view)
+        self._act_src = self.actions if int_actions else self.clamped.unsqueeze(0).expand_as(self.actions)
         obs, _ = vec_env.reset()
         self._stage_obs(obs)
         self._stage_masks()
@@ -561,6 +584,16 @@ class SyncStepRolloutGenerator(RolloutGenerator):
         self.logprobs[s].copy_(logp)
         self.values[s].copy_(v)
 
+    def _sde_step(self, s: int) -> None:
+        if s == 0 or (self.sde_sample_freq > 0 and s % self.sde_sample_freq == 0):
+            self._sde_reset_noise()
+        self._sde_sample(*self._policy_forward(self.policy.network.sde_params_and_value), s)
+
+    def _forward_sample_step(self, s: int) -> None:
+        """Discrete, Box and MultiDiscrete heads: the forward chosen at construction (module, wide-MLP kernels
+        or the MultiDiscrete logits), then the head's sampler into slot s."""
+        self._sample(*self._policy_forward(self._fwd), s)
+
     def _layer_ptrs(self):
         """The two networks' six weight / bias pointers as ctypes arrays, rebuilt only when a
         parameter's storage moved (the flat-buffer views keep theirs across updates)."""
@@ -598,14 +631,14 @@ class SyncStepRolloutGenerator(RolloutGenerator):
     # an observation batch at least this large goes host -> device straight from the env's array
     _DIRECT_OBS_BYTES = 1 << 20
 
-    def _stage_obs(self, obs: np.ndarray, dst: Optional[torch.Tensor] = None) -> None:
+    def _stage_obs(self, obs: np.ndarray) -> None:
         """The next observation batch into next_obs_dev.  Large batches (C3 Pong: 1024 x 4x84x84 u8,
         29 MB) are copied straight from the env's pageable array: HIP's pageable path (~0.54 ms,
         ~53 GB/s, returns when the copy is done) is as fast as the DMA from pinned memory alone,
         while staging through the pinned buffer first costs a single-threaded host memcpy of the
         whole batch (1.35 ms; profiles/r2s_rollout_timing.txt).  Small batches keep the pinned
         buffer and an asynchronous copy."""
-        dst = self.next_obs_dev if dst is None else dst
+        dst = self.next_obs_dev
         if (obs.nbytes >= self._DIRECT_OBS_BYTES and isinstance(obs, np.ndarray) and obs.flags.c_contiguous
                 and obs.flags.writeable and torch.from_numpy(obs[:0]).dtype == self.obs_dtype
                 and obs.shape == tuple(dst.shape)):
@@ -655,107 +688,61 @@ class SyncStepRolloutGenerator(RolloutGenerator):
     @torch.no_grad()
     def _rollout(self, output_next_values: bool) -> Optional[torch.Tensor]:
         self.policy.eval()
-        net = self.policy.network
-        # the fused CartPole-class step reads its slot directly: each step's next observations and episode
-        # starts go host -> device straight into slot s + 1 (two device copies per step fewer); the other
-        # policies' graph-replayed forwards read the fixed next_obs_dev buffer, so they keep the slot copy
-        direct = self.fused_step is not None and os.environ.get("RAI_ROLLOUT_DIRECT", "1") != "0"
-        if direct and self.action_masks is None and os.environ.get("RAI_ROLLOUT_NATIVE", "1") != "0":
-            if os.environ.get("RAI_ROLLOUT_MAPPED", "1") != "0" and self.obs_dtype == torch.float32:
-                self._fused_step_loop_mapped()
-            else:
-                self._fused_step_loop()
-            return self._finish_rollout(output_next_values)
-        for s in range(self.n_steps):
-            if self.sde is not None and (s == 0 or (self.sde_sample_freq > 0 and s % self.sde_sample_freq == 0)):
-                self._sde_reset_noise()
-            if not direct or s == 0:
-                self.obs[s].copy_(self.next_obs_dev)
-                self.episode_starts[s].copy_(self.next_episode_starts)
-            if self.action_masks is not None:
-                self.action_masks[s].copy_(self.next_masks_dev)
-            if self.fused_step is not None:
-                self._fused_step(s)
-            elif self.gridnet:
-                self._gridnet_step(s)
-            elif self.sde is not None:
-                self._sde_sample(*self._policy_forward(net.sde_params_and_value), s)
-            elif self.multidiscrete:
-                self._sample(*self._policy_forward(net.md_logits_and_value), s)
-            else:
-                params, v = self._policy_forward(self._wide_fwd if self._wide_fwd is not None
-                                                 else net.dist_params_and_value)
-                self._sample(params, v, s)
-            src = self.actions[s] if (self.discrete or self.gridnet or self.multidiscrete) else self.clamped
-            self.h_act.copy_(src, non_blocking=True)
-            self._act_ready.record()
-            self._act_ready.synchronize()
-            obs, rew, term, trunc, info = self.vec_env.step(self.h_act.numpy())
-            if info and "episode" in info:
-                done_mask = np.asarray(info.get("_episode", np.ones(self.num_envs, dtype=bool)))
-                self.episode_returns.extend(np.asarray(info["episode"]["r"])[done_mask].tolist())
-                self.episode_lengths.extend(np.asarray(info["episode"]["l"])[done_mask].tolist())
-            np.copyto(self.h_rew.numpy(), rew, casting="same_kind")
-            np.logical_or(term, trunc, out=self.h_done.numpy())
-            self.rewards[s].copy_(self.h_rew, non_blocking=True)
-            into_slot = direct and s + 1 < self.n_steps
-            (self.episode_starts[s + 1] if into_slot else self.next_episode_starts).copy_(self.h_done,
-                                                                                           non_blocking=True)
-            self._stage_obs(obs, self.obs[s + 1] if into_slot else None)
-            self._stage_masks()
+        if self._mapped_loop:
+            self._mapped_step_loop()
+        else:
+            h_rew, h_done = self.h_rew.numpy(), self.h_done.numpy()
+            for s in range(self.n_steps):
+                self._slot_copies(s)
+                self._policy_step(s)
+                obs = self._env_step(self._actions_to_host(s), h_rew, h_done)
+                self._results_to_device(s)
+                self._stage_next(obs)
         return self._finish_rollout(output_next_values)
 
-    def _fused_step_loop(self) -> None:
-        """The CartPole-class env-step loop with one native call per host <-> device hand-off: the fused
-        policy step (forward, sample, slot writes) into slot s, the actions copied to the pinned host
-        buffer and waited for (rai_copy_d2h_sync), the host env step, then the rewards, terminations and
-        next observations copied straight into their slots (rai_copy_h2d_multi).  Same kernels, same
-        sampler stream and the same slot contents as the generic loop above (RAI_ROLLOUT_NATIVE=0); the
-        per-step torch copy / event dispatches it replaces cost ~45 us of the ~95 us step at C2."""
-        L = _lib.lib()
-        sp = self.fused_step
-        pi, v = self._layer_ptrs()
-        st = _lib.stream_handle(self.device)
-        N, T = self.num_envs, self.n_steps
-        self.obs[0].copy_(self.next_obs_dev)
-        self.episode_starts[0].copy_(self.next_episode_starts)
-        slot = lambda t: (t.data_ptr(), t[0].numel() * t.element_size())  # base, bytes per step slot
-        (ob, obs_b), (ab, act_b), (lb, lp_b), (vb, v_b), (rb, rew_b), (eb, es_b) = (
-            slot(self.obs), slot(self.actions), slot(self.logprobs), slot(self.values), slot(self.rewards),
-            slot(self.episode_starts))
-        h_act, h_rew, h_done, h_obs = self.h_act, self.h_rew, self.h_done, self.h_obs
-        assert h_act.numel() * h_act.element_size() == act_b and h_obs.numel() * h_obs.element_size() == obs_b
-        h_act_np, h_rew_np, h_done_np, h_obs_np = h_act.numpy(), h_rew.numpy(), h_done.numpy(), h_obs.numpy()
-        dst = (C.c_void_p * 3)()
-        src = (C.c_void_p * 3)(h_rew.data_ptr(), h_done.data_ptr(), h_obs.data_ptr())
-        nbytes = (C.c_int64 * 3)(rew_b, es_b, obs_b)
-        last = (self.next_episode_starts.data_ptr(), self.next_obs_dev.data_ptr())
-        in_dim, n_act, act_fn = sp["in_dim"], sp["n_act"], sp["activation"]
-        for s in range(T):
-            rc = L.rai_mlp_policy_step(pi, v, ob + s * obs_b, N, in_dim, 64, n_act, act_fn, self.seed, self.rng_offset,
-                                       ab + s * act_b, lb + s * lp_b, vb + s * v_b, st)
-            if rc:
-                _lib.check(rc, "rai_mlp_policy_step")
-            self.rng_offset += 1
-            rc = L.rai_copy_d2h_sync(ab + s * act_b, h_act_np.ctypes.data, act_b, st)
-            if rc:
-                _lib.check(rc, "rai_copy_d2h_sync")
-            obs, rew, term, trunc, info = self.vec_env.step(h_act_np)
-            if info and "episode" in info:
-                done_mask = np.asarray(info.get("_episode", np.ones(self.num_envs, dtype=bool)))
-                self.episode_returns.extend(np.asarray(info["episode"]["r"])[done_mask].tolist())
-                self.episode_lengths.extend(np.asarray(info["episode"]["l"])[done_mask].tolist())
-            np.copyto(h_rew_np, rew, casting="same_kind")
-            np.logical_or(term, trunc, out=h_done_np)
-            np.copyto(h_obs_np, obs, casting="same_kind")
-            dst[0] = rb + s * rew_b
-            if s + 1 < T:
-                dst[1], dst[2] = eb + (s + 1) * es_b, ob + (s + 1) * obs_b
-            else:
-                dst[1], dst[2] = last
-            rc = L.rai_copy_h2d_multi(3, dst, src, nbytes, st)
-            if rc:
-                _lib.check(rc, "rai_copy_h2d_multi")
+    # -- the generic step's phases (tools/rollout_timing.py times these same methods) --------
+    def _slot_copies(self, s: int) -> None:
+        """The staged observations, episode starts and masks into slot s (the graph-replayed forwards read
+        the fixed next_obs_dev buffer, so the slot is a copy of it)."""
+        self.obs[s].copy_(self.next_obs_dev)
+        self.episode_starts[s].copy_(self.next_episode_starts)
+        if self.action_masks is not None:
+            self.action_masks[s].copy_(self.next_masks_dev)
+
+    def _policy_step(self, s: int) -> None:
+        """Forward, sample and the action / log-prob / value writes into slot s, by the step chosen at
+        construction."""
+        self._step_fn(self, s)
+
+    def _actions_to_host(self, s: int) -> np.ndarray:
+        self.h_act.copy_(self._act_src[s], non_blocking=True)
+        self._act_ready.record()
+        self._act_ready.synchronize()
+        return self.h_act.numpy()
+
+    def _env_step(self, actions: np.ndarray, rew_dst: np.ndarray, done_dst: np.ndarray) -> np.ndarray:
+        """The host env step; its results but the observations are taken here, the observations returned."""
+        obs, rew, term, trunc, info = self.vec_env.step(actions)
+        self._take_env_results(rew, term, trunc, info, rew_dst, done_dst)
+        return obs
+
+    def _take_env_results(self, rew, term, trunc, info, rew_dst: np.ndarray, done_dst: np.ndarray) -> None:
+        """Finished episodes into episode_returns / episode_lengths; the rewards and term | trunc into the
+        two host destinations (pinned buffers in the generic loop, host-mapped arrays in the mapped one)."""
+        if info and "episode" in info:
+            done_mask = np.asarray(info.get("_episode", np.ones(self.num_envs, dtype=bool)))
+            self.episode_returns.extend(np.asarray(info["episode"]["r"])[done_mask].tolist())
+            self.episode_lengths.extend(np.asarray(info["episode"]["l"])[done_mask].tolist())
+        np.copyto(rew_dst, rew, casting="same_kind")
+        np.logical_or(term, trunc, out=done_dst)
+
+    def _results_to_device(self, s: int) -> None:
+        self.rewards[s].copy_(self.h_rew, non_blocking=True)
+        self.next_episode_starts.copy_(self.h_done, non_blocking=True)
+
+    def _stage_next(self, obs: np.ndarray) -> None:
+        self._stage_obs(obs)
+        self._stage_masks()
 
     def _mapped_buffers(self) -> Dict[str, tuple]:
         """Host-mapped pinned staging buffers (rai_host_alloc: coherent host memory the policy-step kernel
@@ -781,12 +768,12 @@ class SyncStepRolloutGenerator(RolloutGenerator):
             self._mapped = bufs
         return self._mapped
 
-    def _fused_step_loop_mapped(self) -> None:
+    def _mapped_step_loop(self) -> None:
         """The CartPole-class env-step loop with ONE launch and one stream wait per env step: the policy
         step kernel reads the env's next observations, rewards and terminations straight from host-mapped
         pinned memory into their slots and writes the sampled actions to host-mapped memory too
         (rai_mlp_policy_step_mapped), so no per-step copy is issued.  Same kernel arithmetic and sampler
-        stream as _fused_step_loop (RAI_ROLLOUT_MAPPED=0), bit-identical buffers."""
+        stream as the generic loop with _fused_step (RAI_ROLLOUT_MAPPED=0), bit-identical buffers."""
         L = _lib.lib()
         sp = self.fused_step
         pi, v = self._layer_ptrs()
@@ -803,6 +790,7 @@ class SyncStepRolloutGenerator(RolloutGenerator):
             slot(self.episode_starts))
         assert obs_np.nbytes == obs_b and act_np.nbytes == act_b and rew_np.nbytes == rew_b and done_np.nbytes == es_b
         in_dim, n_act, act_fn = sp["in_dim"], sp["n_act"], sp["activation"]
+        env_step, take_results = self.vec_env.step, self._take_env_results
         for s in range(T):
             if s == 0:  # slot 0 already holds next_obs_dev / next_episode_starts (device copies above)
                 rc = L.rai_mlp_policy_step_mapped(pi, v, None, ob, N, in_dim, 64, n_act, act_fn, self.seed,
@@ -818,13 +806,8 @@ class SyncStepRolloutGenerator(RolloutGenerator):
             rc = L.rai_stream_sync(st)
             if rc:
                 _lib.check(rc, "rai_stream_sync")
-            obs, rew, term, trunc, info = self.vec_env.step(act_np)
-            if info and "episode" in info:
-                done_mask = np.asarray(info.get("_episode", np.ones(self.num_envs, dtype=bool)))
-                self.episode_returns.extend(np.asarray(info["episode"]["r"])[done_mask].tolist())
-                self.episode_lengths.extend(np.asarray(info["episode"]["l"])[done_mask].tolist())
-            np.copyto(rew_np, rew, casting="same_kind")
-            np.logical_or(term, trunc, out=done_np)
+            obs, rew, term, trunc, info = env_step(act_np)
+            take_results(rew, term, trunc, info, rew_np, done_np)
             np.copyto(obs_np, obs.reshape(obs_np.shape), casting="same_kind")
         # the last step's results: rewards -> slot T - 1, starts / observations -> next_* (async copies from
         # the mapped buffers; the next rollout writes them only after its first stream wait)

@@ -842,33 +842,88 @@ def test_wide_rollout_forward_matches_module(kind, N, monkeypatch):
     np.testing.assert_allclose(l1[same], l0[same], rtol=1e-4, atol=1e-5)
 
 
-def test_fused_rollout_direct_slot_staging_is_identical(monkeypatch):
-    """The CartPole-class rollout stages each step's next observations and episode starts straight into
-    slot s + 1 (RAI_ROLLOUT_DIRECT, default on) instead of through next_obs_dev / next_episode_starts
-    and a device copy: two seeded rollouts (two updates' worth, so the second starts from the first's
-    carried-over state), one each way, give bit-identical buffers and bootstrap values."""
+def _select_rollout_loop(monkeypatch, generic: bool) -> None:
+    """A CartPole-class generator built next takes its default (mapped) step loop, or the generic one (the
+    RAI_ROLLOUT_MAPPED=0 diagnostic)."""
+    if generic:
+        monkeypatch.setenv("RAI_ROLLOUT_MAPPED", "0")
+    else:
+        monkeypatch.delenv("RAI_ROLLOUT_MAPPED", raising=False)
+
+
+def test_fused_rollout_mapped_loop_is_identical(monkeypatch):
+    """The CartPole-class rollout hands each step's observations, rewards, terminations and actions over
+    through host-mapped memory inside the policy-step launch (the default) instead of staging through
+    next_obs_dev / next_episode_starts, device copies into slot s and a D2H action copy (the generic loop,
+    RAI_ROLLOUT_MAPPED=0): two seeded rollouts (two updates' worth, so the second starts from the first's
+    carried-over state), one each way, give bit-identical buffers and bootstrap values, at N = 96 and at
+    N = 40 (a ragged last 32-row workgroup of the step kernel)."""
     from rl_algo_impls_amd.envs import SyntheticVecEnv
     from rl_algo_impls_amd.policy import ActorCritic
 
-    out = []
-    for direct, native, mapped in (("1", "1", "1"), ("1", "1", "0"), ("1", "0", "0"), ("0", "0", "0")):
-        monkeypatch.setenv("RAI_ROLLOUT_DIRECT", direct)
-        monkeypatch.setenv("RAI_ROLLOUT_NATIVE", native)  # the native staging loop (default) vs torch copies
-        monkeypatch.setenv("RAI_ROLLOUT_MAPPED", mapped)  # host-mapped hand-off in the policy-step kernel
+    names = ("obs", "actions", "rewards", "episode_starts", "values", "logprobs", "next_values",
+             "next_episode_starts", "advantages")
+    for N in (96, 40):
+        out = []
+        for generic in (False, True):
+            _select_rollout_loop(monkeypatch, generic)
+            torch.manual_seed(3)
+            env = SyntheticVecEnv(N, "cartpole", seed=5)
+            policy = ActorCritic(env).to(DEV)
+            gen = SyncStepRolloutGenerator(policy, env, n_steps=16, seed=9)
+            assert gen.fused_step is not None and gen._mapped_loop == (not generic)
+            res = []
+            for _ in range(2):
+                r = gen.rollout(gamma=0.98, gae_lambda=0.8)
+                torch.cuda.synchronize()
+                res.append([t.detach().cpu().numpy().copy() for t in (
+                    gen.obs, gen.actions, gen.rewards, gen.episode_starts, gen.values, gen.logprobs, r.next_values,
+                    r.next_episode_starts, r.advantages)])
+            out.append(res)
+        for i, (a, b) in enumerate(zip(*out)):
+            for name, x, y in zip(names, a, b):
+                np.testing.assert_array_equal(x, y, err_msg=f"N = {N}, rollout {i}, {name}")
+
+
+class _EpisodeRecordingEnv:
+    """A vector env passed through unchanged, recording every finished episode's return and length as the
+    env emits them (info["episode"] under info["_episode"])."""
+
+    def __init__(self, env):
+        self._env = env
+        self.returns, self.lengths = [], []
+
+    def __getattr__(self, name):
+        return getattr(self._env, name)
+
+    def step(self, actions):
+        out = self._env.step(actions)
+        info = out[4]
+        if "episode" in info:
+            done = info["_episode"]
+            self.returns += info["episode"]["r"][done].tolist()
+            self.lengths += info["episode"]["l"][done].tolist()
+        return out
+
+
+def test_rollout_records_finished_episodes_in_both_loops(monkeypatch):
+    """episode_returns / episode_lengths hold exactly the env's finished episodes, in order (the last 100), in
+    the mapped loop and in the generic one (RAI_ROLLOUT_MAPPED=0), which see the same episodes."""
+    from rl_algo_impls_amd.envs import CartPoleVecEnv
+    from rl_algo_impls_amd.policy import ActorCritic
+
+    got = []
+    for generic in (False, True):
+        _select_rollout_loop(monkeypatch, generic)
         torch.manual_seed(3)
-        env = SyntheticVecEnv(96, "cartpole", seed=5)
-        policy = ActorCritic(env).to(DEV)
-        gen = SyncStepRolloutGenerator(policy, env, n_steps=16, seed=9)
-        assert gen.fused_step is not None
-        res = []
+        env = _EpisodeRecordingEnv(CartPoleVecEnv(40, seed=6))
+        gen = SyncStepRolloutGenerator(ActorCritic(env).to(DEV), env, n_steps=16, seed=9)
+        assert gen.fused_step is not None and gen._mapped_loop == (not generic)
         for _ in range(2):
-            r = gen.rollout(gamma=0.98, gae_lambda=0.8)
-            torch.cuda.synchronize()
-            res.append([t.detach().cpu().numpy().copy() for t in (gen.obs, gen.actions, gen.rewards, gen.episode_starts,
-                                                                   gen.values, gen.logprobs, r.next_values,
-                                                                   r.next_episode_starts, r.advantages)])
-        out.append(res)
-    for other in out[1:]:
-        for a, b in zip(out[0], other):
-            for x, y in zip(a, b):
-                np.testing.assert_array_equal(x, y)
+            gen.rollout(gamma=0.98, gae_lambda=0.8)
+        torch.cuda.synchronize()
+        assert len(env.returns) >= 10
+        assert list(gen.episode_returns) == env.returns[-100:]
+        assert list(gen.episode_lengths) == env.lengths[-100:]
+        got.append((list(gen.episode_returns), list(gen.episode_lengths)))
+    assert got[0] == got[1]

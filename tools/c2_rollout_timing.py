@@ -1,6 +1,7 @@
 """Diagnostic: the C2 (CartPole 4096 envs x 128 steps) rollout's per-env-step wall time split by host
-timers: the whole rollout, then each phase of the step loop alone (env.step, the fused policy step, the
-D2H action copy + wait, the three H2D copies).  Not part of the product or the tests.
+timers: the whole rollout, then each phase of the step loop alone (env.step, the fused policy step and,
+from the generic loop that RAI_ROLLOUT_MAPPED=0 selects, the D2H action copy + wait and the three H2D
+copies), each through the generator's own phase method.  Not part of the product or the tests.
 
     python tools/c2_rollout_timing.py
 """
@@ -10,7 +11,6 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import _pkgload  # noqa: E402
@@ -59,22 +59,13 @@ def timed(name, fn, n=T * reps):
     print(f"  {name:40s} {us:8.1f} us")
 
 
+print("phases alone (the copy rows are the generic loop's, RAI_ROLLOUT_MAPPED=0; the mapped loop issues none):")
 acts = gen.h_act.numpy().copy()
 timed("env.step (host, numpy)", lambda: env.step(acts))
-timed("fused policy step (launch, async)", lambda: gen._fused_step(0))
-timed("fused policy step + sync", lambda: (gen._fused_step(0), sync()))
-
-
-def d2h():
-    gen.h_act.copy_(gen.actions[0], non_blocking=True)
-    gen._act_ready.record()
-    gen._act_ready.synchronize()
-
-
-timed("D2H actions + event wait", d2h)
+timed("fused policy step (launch, async)", lambda: gen._policy_step(0))
+timed("fused policy step + sync", lambda: (gen._policy_step(0), sync()))
+timed("D2H actions + event wait", lambda: gen._actions_to_host(0))
 obs, rew, term, trunc, info = env.step(acts)
-timed("3 H2D copies (rew, done, obs)", lambda: (gen.rewards[0].copy_(gen.h_rew, non_blocking=True),
-                                                gen.episode_starts[1].copy_(gen.h_done, non_blocking=True),
-                                                gen._stage_obs(obs, gen.obs[1])))
-timed("np.copyto rew + logical_or done", lambda: (np.copyto(gen.h_rew.numpy(), rew, casting="same_kind"),
-                                                  np.logical_or(term, trunc, out=gen.h_done.numpy())))
+timed("3 H2D copies (rew, done, obs)", lambda: (gen._results_to_device(0), gen._stage_next(obs)))
+h_rew, h_done = gen.h_rew.numpy(), gen.h_done.numpy()
+timed("np.copyto rew + logical_or done", lambda: gen._take_env_results(rew, term, trunc, {}, h_rew, h_done))

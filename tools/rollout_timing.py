@@ -1,6 +1,10 @@
 """Diagnostic: where one env step of a bench config's rollout spends its wall time (host timers with
 a device synchronize after every phase), next to the unsynchronised rollout, plus the host->device
-staging alternatives for the step's observation batch.  Not part of the product or the tests.
+staging alternatives for the step's observation batch.  The phases are the generic step loop's own
+methods (SyncStepRolloutGenerator._slot_copies ... _stage_next), so every policy kind is timed as it
+runs; forward and sample are one "policy step" row (the earlier "forward graph" and "sample" rows,
+merged).  A CartPole-class config is timed in this generic form, not its mapped loop.  Not part of the
+product or the tests.
 
     python tools/rollout_timing.py --config pong --steps 64
 """
@@ -48,47 +52,36 @@ sync()
 whole = time.perf_counter() - t0
 print(f"whole rollout {T} steps x {N} envs: {whole * 1e3:.1f} ms = {whole * 1e3 / T:.3f} ms/step", flush=True)
 
-# phase split of the generic (non-fused, non-GridNet) step, synchronising after every phase
-net = policy.network
-ph = {k: [] for k in ("slot copies", "forward graph", "sample", "D2H act + sync", "env.step",
-                      "reward/done H2D", "stage obs (+ masks)")}
+# the generic step's phases, the generator's own methods, synchronising after every phase
+h_rew, h_done = gen.h_rew.numpy(), gen.h_done.numpy()
+ph = {k: [] for k in ("slot copies", "policy step", "D2H act + sync", "env.step + results", "reward/done H2D",
+                      "stage obs (+ masks)")}
+
+
+def lap(name, t0):
+    sync()
+    t1 = time.perf_counter()
+    ph[name].append(t1 - t0)
+    return t1
+
+
 policy.eval()
 with torch.no_grad():
     for s in range(args.steps):
         s_ = s % T
-        t = [time.perf_counter()]
-        gen.obs[s_].copy_(gen.next_obs_dev)
-        gen.episode_starts[s_].copy_(gen.next_episode_starts)
-        sync(); t.append(time.perf_counter())
-        if gen.action_masks is not None:
-            gen.action_masks[s_].copy_(gen.next_masks_dev)
-        if gen.fused_step is not None:  # CartPole class: forward + sample in one launch
-            gen._fused_step(s_)
-            sync(); t.append(time.perf_counter())
-        elif gen.gridnet:  # forward graph + GridNet sample in one phase, nothing in "sample"
-            gen._gridnet_step(s_)
-            sync(); t.append(time.perf_counter())
-        else:
-            params, v = gen._policy_forward(net.dist_params_and_value)
-            sync(); t.append(time.perf_counter())
-            gen._sample(params, v, s_)
-        sync(); t.append(time.perf_counter())
-        gen.h_act.copy_(gen.actions[s_] if (gen.discrete or gen.gridnet) else gen.clamped, non_blocking=True)
-        gen._act_ready.record()
-        gen._act_ready.synchronize()
-        t.append(time.perf_counter())
-        obs, rew, term, trunc, info = env.step(gen.h_act.numpy())
-        np.copyto(gen.h_rew.numpy(), rew, casting="same_kind")
-        np.logical_or(term, trunc, out=gen.h_done.numpy())
-        t.append(time.perf_counter())
-        gen.rewards[s_].copy_(gen.h_rew, non_blocking=True)
-        gen.next_episode_starts.copy_(gen.h_done, non_blocking=True)
-        sync(); t.append(time.perf_counter())
-        gen._stage_obs(obs)
-        gen._stage_masks()
-        sync(); t.append(time.perf_counter())
-        for k, a, b in zip(ph, t[:-1], t[1:]):
-            ph[k].append(b - a)
+        t = time.perf_counter()
+        gen._slot_copies(s_)
+        t = lap("slot copies", t)
+        gen._policy_step(s_)
+        t = lap("policy step", t)
+        acts = gen._actions_to_host(s_)
+        t = lap("D2H act + sync", t)
+        obs = gen._env_step(acts, h_rew, h_done)
+        t = lap("env.step + results", t)
+        gen._results_to_device(s_)
+        t = lap("reward/done H2D", t)
+        gen._stage_next(obs)
+        t = lap("stage obs (+ masks)", t)
 tot = 0.0
 for k, v in ph.items():
     m = float(np.median(v)) * 1e3
