@@ -456,6 +456,49 @@ int rai_clip_optim_step(float* params, float* grads, float* state1, float* state
                         void* stream);
 
 /* --------------------------------------------------------------------------
+ * The run-wise form of the step above, for PPO's freeze_policy_head /
+ * freeze_value_head / freeze_backbone (rl_algo_impls/ppo/ppo.py:280-285,
+ * 412-413).  torch's semantics are per tensor: a frozen tensor has no .grad,
+ * clip_grad_norm_ sums over the others, and Adam.step() skips it entirely (no
+ * moment update, no state['step'] increment), so after unfreeze() the tensors
+ * carry different step counts and bias corrections.
+ *
+ * A run is a maximal stretch of the flat buffer whose elements share "trainable
+ * or not" and one step count.  runs (DEVICE memory, n_runs entries, 1 ..
+ * RAI_OPTIM_MAX_RUNS) partition [0, P) in ascending order; boundaries are
+ * arbitrary element offsets.  Same two launches, same fixed order:
+ *   K1  fp64 partial sums of squares over the ACTIVE runs; opt_step += 1
+ *   K2  the norm (norms[state->norm_index++]) and clip coefficient from them;
+ *       active run: rai_clip_optim_step's per-element update with bias
+ *         corrections at step opt_step - lag;
+ *       frozen run: zeros stored to the gradient (fused backward kernels write
+ *         a frozen head's weight gradients through raw pointers), p / m / v
+ *         neither loaded nor stored.
+ * The table is never written on the device and lag is constant through an
+ * update: the caller adds the steps a frozen run sat out to its lag afterwards
+ * and may rewrite the table between updates without recapturing a graph.
+ * The caller guarantees a well-formed table (0 <= lag <= opt_step for active
+ * runs); runs are clipped to [0, P) on the device.  RMSprop: a frozen run
+ * keeps its square average; lag is unused.
+ * One active run {0, P, 0, 1} is bit-identical to rai_clip_optim_step.
+ * n_runs out of range: RAI_E_SHAPE; NULL runs: RAI_E_NULLPTR; otherwise
+ * rai_clip_optim_step's codes.  Workspace: rai_optim_workspace_bytes(P).
+ * ------------------------------------------------------------------------ */
+#define RAI_OPTIM_MAX_RUNS 64
+typedef struct rai_optim_run {
+  int64_t begin, end; /* [begin, end) in elements */
+  int64_t lag;        /* optimizer steps this run sat out: its Adam step is state->opt_step - lag */
+  int32_t active;     /* 0: frozen in this update */
+  int32_t pad;
+} rai_optim_run;
+
+int rai_clip_optim_step_runs(float* params, float* grads, float* state1, float* state2, int64_t P,
+                             const rai_optim_hparams* hp, rai_train_state* state,
+                             const rai_optim_run* runs, int32_t n_runs, float* norms,
+                             int32_t max_norms, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
+/* --------------------------------------------------------------------------
  * Multi-field row gather: dst_f[i] = src_f[idx[i]] for up to RAI_MAX_FIELDS
  * fields of arbitrary row size (bytes).  Replaces the minibatch fancy-index
  * gather of rl_algo_impls/rollout/rollout.py:56-69 / vec_rollout.py:166-175;

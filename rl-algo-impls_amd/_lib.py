@@ -155,6 +155,16 @@ class OptimHparams(C.Structure):
     ]
 
 
+RAI_OPTIM_MAX_RUNS = 64
+
+
+class OptimRun(C.Structure):
+    """Mirror of rai_optim_run (one entry of rai_clip_optim_step_runs' device table)."""
+
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lag", C.c_int64), ("active", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 class TrainState(C.Structure):
     _fields_ = [
         ("opt_step", C.c_int64),
@@ -178,6 +188,8 @@ _SIGNATURES = {
                                        _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "rai_optim_workspace_bytes": (_i64, [_i64]),
     "rai_clip_optim_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "rai_clip_optim_step_runs": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64,
+                                           _vp]),
     "rai_gather_rows": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "rai_feistel_permutation": (C.c_int, [_i64, C.c_uint64, _vp, _vp]),
     "rai_copy_d2h_sync": (C.c_int, [_vp, _vp, _i64, _vp]),

@@ -468,7 +468,8 @@ class ConvBiasReLU(torch.autograd.Function):
         x, w, b, y = ctx.saved_tensors
         stride, padding, key, direct_b, direct_w, flatten, zshape, mfma = ctx.conf
         u8 = x.dtype == torch.uint8  # (never needs an input gradient)
-        if (mfma and _CONV_FUSE_RELU_BWD and not flatten and direct_b and direct_w
+        need_dw = ctx.needs_input_grad[1]  # False: a frozen layer under a trainable input, no weight-gradient job
+        if (mfma and _CONV_FUSE_RELU_BWD and not flatten and direct_b and direct_w and need_dw
                 and (not ctx.needs_input_grad[0] or _CONV_MFMA_DGRAD)
                 and w.grad.is_contiguous(memory_format=torch.channels_last) and w.grad.data_ptr() % 16 == 0
                 and b.grad.data_ptr() % 16 == 0 and y.is_contiguous(memory_format=torch.channels_last)):
@@ -499,6 +500,8 @@ class ConvBiasReLU(torch.autograd.Function):
             dx = None
             if need_dx:
                 dx = _conv_dgrad(x, dz, w, stride)
+            if not need_dw:
+                return dx, None, db, None, None, None, None, None
             g = w.grad
             if (direct_w and g.is_contiguous(memory_format=torch.channels_last) and g.data_ptr() % 16 == 0):
                 # partial tiles now; their reduction into the flat .grad joins the other layers' in one
@@ -514,8 +517,8 @@ class ConvBiasReLU(torch.autograd.Function):
                     dw = None
             return dx, dw, db, None, None, None, None, None
         dx, dw, _ = torch.ops.aten.convolution_backward(dz, x, w, None, _pair(stride), _pair(padding), [1, 1],
-                                                        False, [0, 0], 1, [need_dx, True, False])
-        if direct_w:  # accumulated with the other layers' at direct_grads() exit
+                                                        False, [0, 0], 1, [need_dx, need_dw, False])
+        if direct_w and need_dw:  # accumulated with the other layers' at direct_grads() exit
             ctx.pending.add(w, dw)
             dw = None
         return dx, dw, db, None, None, None, None, None
@@ -542,7 +545,9 @@ class LinearBiasReLU(torch.autograd.Function):
         key, direct_b, direct_w = ctx.conf
         dz, db = _bias_relu_bwd(dy.contiguous(), y, b, _WS.get(key, int(y.shape[1]), y.device), direct_b)
         dx = torch.mm(dz, w) if ctx.needs_input_grad[0] else None
-        if direct_w:
+        if not ctx.needs_input_grad[1]:  # a frozen layer: no weight-gradient GEMM
+            dw = None
+        elif direct_w:
             w.grad.addmm_(dz.t(), x)  # beta = 1: the GEMM accumulates into the flat gradient view
             dw = None
             notify_grad_written(w)  # data parallel: this layer's gradient bucket may go (dp_buckets)
@@ -685,8 +690,9 @@ class FcReluHeads(torch.autograd.Function):
             wpi.grad.data_ptr(), bpi.grad.data_ptr(), wv.grad.data_ptr(), bv.grad.data_ptr(), b.grad.data_ptr(), 1,
             ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)), "rai_categorical_critic_heads_bwd_relu")
         dx = torch.mm(dz, w) if ctx.needs_input_grad[0] else None
-        w.grad.addmm_(dz.t(), x)  # beta = 1: the GEMM accumulates into the flat gradient view
-        notify_grad_written(w)  # data parallel: this layer's gradient bucket may go (dp_buckets)
+        if ctx.needs_input_grad[1]:  # (a frozen backbone under trainable heads: the fc's weight gradient is skipped)
+            w.grad.addmm_(dz.t(), x)  # beta = 1: the GEMM accumulates into the flat gradient view
+            notify_grad_written(w)  # data parallel: this layer's gradient bucket may go (dp_buckets)
         return dx, None, None, None, None, None, None, None
 
 

@@ -186,7 +186,9 @@ class ConvPool(torch.autograd.Function):
         wc = _weight(w)
         dz = _pool_bwd(_nhwc(dy), am, H, W)
         dx = _conv_dgrad(dz, wc) if ctx.needs_input_grad[0] else None
-        dw, db = _conv_wgrad(key, x, dz, w, b, False, direct, x_div)
+        dw = db = None  # (a frozen layer under a trainable input: no weight-gradient launch)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = _conv_wgrad(key, x, dz, w, b, False, direct, x_div)
         return dx, dw, db, None, None
 
 
@@ -223,10 +225,15 @@ class ResBlock(torch.autograd.Function):
                 dout = _nhwc(torch.ops.aten.threshold_backward(dy.reshape(B, C, H, W), y.view(B, C, H, W), 0))
         else:
             dout = _nhwc(dy)
-        dh = _conv_dgrad(dout, _weight(w2), m=h)
-        dw2, db2 = _conv_wgrad(key2, h, dout, w2, b2, True, direct2)
-        dx = _conv_dgrad(dh, _weight(w1), m=x, res=dout) if ctx.needs_input_grad[0] else None
-        dw1, db1 = _conv_wgrad(key1, x, dh, w1, b1, True, direct1)
+        need = ctx.needs_input_grad  # a frozen layer's weight-gradient launch is skipped
+        need1 = need[1] or need[2]
+        dh = _conv_dgrad(dout, _weight(w2), m=h) if need[0] or need1 else None
+        dw1 = db1 = dw2 = db2 = None
+        if need[3] or need[4]:
+            dw2, db2 = _conv_wgrad(key2, h, dout, w2, b2, True, direct2)
+        dx = _conv_dgrad(dh, _weight(w1), m=x, res=dout) if need[0] else None
+        if need1:
+            dw1, db1 = _conv_wgrad(key1, x, dh, w1, b1, True, direct1)
         return dx, dw1, db1, dw2, db2, None, None, None
 
 

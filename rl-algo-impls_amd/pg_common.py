@@ -205,7 +205,14 @@ def save_optimizer(optimizer, path: str) -> None:
     torch.save(optimizer.state_dict(), os.path.join(path, OPTIMIZER_FILENAME))
 
 
-def load_optimizer(optimizer, path: str, device) -> None:
+def load_optimizer(optimizer, path: str, device, per_parameter_steps: bool = False) -> None:
+    """per_parameter_steps: the trainer has the freeze_* options (PPO) and keeps a policy whose parameters are
+    at different optimizer steps on paths that honour them; the others refuse such a checkpoint."""
     p = os.path.join(path, OPTIMIZER_FILENAME)
     if os.path.exists(p):
-        optimizer.load_state_dict(torch.load(p, map_location=device, weights_only=True))
+        sd = torch.load(p, map_location=device, weights_only=True)
+        steps = {int(float(s["step"])) for s in sd["state"].values()}
+        if not per_parameter_steps and (len(steps) > 1 or (steps and len(sd["state"]) < len(optimizer.flat.params))):
+            raise NotImplementedError("optimizer.pt holds per-parameter step counts that differ (written after a "
+                                      "PPO freeze_* phase); only PPO continues from such a checkpoint")
+        optimizer.load_state_dict(sd)

@@ -51,9 +51,12 @@ class PPO(PPOEpochKernels, PPODataParallel):
                  guide_probability=None, normalize_advantages_after_scaling: bool = False,
                  autocast_loss: bool = False, vf_loss_fn: str = "mse_loss", vf_weights=None,
                  teacher_kl_loss_coef=None, teacher_kl_loss_fn=None, teacher_loss_importance_sampling=True):
-        unsupported(freeze_policy_head=freeze_policy_head, freeze_value_head=freeze_value_head,
-                    freeze_backbone=freeze_backbone, switch_range=switch_range is not None,
-                    guide_probability=guide_probability is not None, autocast_loss=autocast_loss)
+        unsupported(switch_range=switch_range is not None, guide_probability=guide_probability is not None,
+                    autocast_loss=autocast_loss)
+        # ppo.py:280-285,412-413: policy.freeze(...) around the update; HyperparamTransitions sets these
+        self.freeze_policy_head = freeze_policy_head
+        self.freeze_value_head = freeze_value_head
+        self.freeze_backbone = freeze_backbone
         assert not (normalize_advantage and standardize_advantage), "Cannot both normalize and standardize advantage"
         # the teacher-KL term (ppo.py:188-190,363-371): on when the coefficient is truthy; the loss fn's
         # add_to_batch runs after every rollout whenever the fn is set
@@ -237,11 +240,51 @@ class PPO(PPOEpochKernels, PPODataParallel):
                 K_box[0] = value_columns(v)
             d_logp, d_ent, d_v = launch_loss(self.blocks, logp, ent, v, logprobs, values, adv, ret, K_box[0],
                                              teacher_logp=teacher_logp)
-            torch.autograd.backward([logp, ent, v], [d_logp, d_ent, d_v])
+            # (a frozen head under a frozen backbone leaves its outputs without a graph: freeze_*)
+            outs = [(o, d) for o, d in ((logp, d_logp), (ent, d_ent), (v, d_v)) if o.requires_grad]
+            torch.autograd.backward([o for o, _ in outs], [d for _, d in outs])
+
+    def _freeze_on(self) -> bool:
+        return bool(self.freeze_policy_head or self.freeze_value_head or self.freeze_backbone)
 
     def update(self, r) -> Tuple[np.ndarray, np.ndarray, int]:
         """All epochs x minibatches of one update, enqueued without host syncs;
-        returns the per-minibatch stats rows and grad norms (one D2H copy)."""
+        returns the per-minibatch stats rows and grad norms (one D2H copy).
+
+        With a freeze_* flag set the update runs between policy.freeze(...) and policy.unfreeze()
+        (ppo.py:280-285,412-413).  torch's semantics are per tensor: a frozen tensor has no gradient,
+        clip_grad_norm_ sums over the others, Adam skips it (no moment update, no step increment).
+        Here the optimizer's frozen mask comes from requires_grad over the flat parameters and the step is
+        rai_clip_optim_step_runs; afterwards the frozen parameters' lag grows by the steps taken.  Such an
+        update, and every later one of a policy whose parameters' step counts differ, runs on the
+        per-minibatch path: the whole-epoch kernels and WideStep carry ONE Adam step count
+        (_fused_kernels_off)."""
+        opt = self.optimizer
+        if not self._freeze_on():
+            if self.world > 1 and opt.lag.any():
+                raise NotImplementedError("parameters at different optimizer steps (after a freeze_* phase) "
+                                          "under data parallel (world > 1)")
+            return self._update(r)
+        if self.world > 1:
+            raise NotImplementedError("freeze_policy_head / freeze_value_head / freeze_backbone under data "
+                                      "parallel (world > 1)")
+        self.policy.freeze(self.freeze_policy_head, self.freeze_value_head, self.freeze_backbone)
+        try:
+            mask = [not p.requires_grad for p in self.flat.params]
+            if all(mask):
+                raise ValueError("every parameter is frozen (freeze_policy_head, freeze_value_head and "
+                                 "freeze_backbone): nothing to train")
+            opt.set_frozen(mask)
+            before = opt.step_count
+            try:
+                return self._update(r)
+            finally:  # also when the update raised part-way: the steps it did take are accounted for
+                opt.account(opt.step_count - before)
+        finally:
+            self.policy.unfreeze()
+            opt.set_frozen([False] * len(self.flat.params))
+
+    def _update(self, r) -> Tuple[np.ndarray, np.ndarray, int]:
         self.last_update_rollout = r
         self._teacher_stats = None
         if self.dp_enabled and self.dp_update_mode == "replicated":
@@ -251,7 +294,7 @@ class PPO(PPOEpochKernels, PPODataParallel):
             self.last_update_rollout = g
             self.dp_enabled = False
             try:
-                out = self.update(g)
+                out = self._update(g)
             finally:
                 self.dp_enabled = True
                 self.last_update_rollout = g
@@ -409,7 +452,11 @@ class PPO(PPOEpochKernels, PPODataParallel):
         # a graph bakes in every device pointer it touches: key it on the ones that can change
         tag = (optim_in_step, wide is not None, buckets is not None, blocks.stats.data_ptr(), blocks.norms.data_ptr(), blocks.hp.data_ptr(),
                blocks.state.data_ptr(), self.flat.flat.data_ptr(), self.flat.grad.data_ptr(),
-               self.optimizer.hp_dev.data_ptr())
+               self.optimizer.hp_dev.data_ptr(),
+               # the captured autograd work differs with requires_grad; the optimizer call bakes in its form,
+               # the table's pointer and its length (the host rewrites the entries between updates)
+               tuple(bool(f) for f in self.optimizer.frozen), self.optimizer._n_runs,
+               self.optimizer.runs_dev.data_ptr())
         if teacher is not None:
             tag += (blocks.teacher.data_ptr(), blocks.teacher_stats.data_ptr())
         g = gu.graph_for(fields, B, tag, xforms)
@@ -466,4 +513,4 @@ class PPO(PPOEpochKernels, PPODataParallel):
         save_optimizer(self.optimizer, path)
 
     def load(self, path: str) -> None:
-        load_optimizer(self.optimizer, path, self.device)
+        load_optimizer(self.optimizer, path, self.device, per_parameter_steps=True)

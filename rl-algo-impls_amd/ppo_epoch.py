@@ -33,9 +33,11 @@ class PPOEpochKernels:
 
     def _fused_kernels_off(self, r=None) -> bool:
         """No fused MLP kernel for this update (of rollout r): force_generic, a teacher term (the fused
-        kernels carry none: the network + rai_ppo_loss_teacher run) or action masks (no mask input: the
-        per-minibatch policy forward receives Batch.action_masks)."""
-        return (self.force_generic or self._teacher_on()
+        kernels carry none: the network + rai_ppo_loss_teacher run), a freeze_* flag or parameters at
+        different optimizer steps after one (the whole-epoch kernels and WideStep carry ONE Adam step
+        count and would apply wrong bias corrections: rai_clip_optim_step_runs runs per minibatch) or
+        action masks (no mask input: the per-minibatch policy forward receives Batch.action_masks)."""
+        return (self.force_generic or self._teacher_on() or self._freeze_on() or not self.optimizer.uniform()
                 or (r is not None and getattr(r, "action_masks", None) is not None))
 
     def fused_mlp_spec(self) -> Optional[dict]:
