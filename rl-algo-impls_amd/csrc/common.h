@@ -15,6 +15,8 @@
 
 static inline hipStream_t rai_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+constexpr float RAI_F32_MIN = -3.4028234663852886e38f;  // torch.finfo(torch.float32).min
+
 // Workgroup barrier for LDS hand-offs only: drains this wave's LDS traffic and meets
 // the other waves, but does NOT wait for outstanding global loads/stores
 // (__syncthreads() adds s_waitcnt vmcnt(0), which exposes prefetch and store latency).

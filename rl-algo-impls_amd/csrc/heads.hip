@@ -22,7 +22,6 @@
 namespace {
 
 constexpr int HD_THREADS = 256;  // 4 waves, one row each
-constexpr float HD_F32_MIN = -3.4028234663852886e38f;
 
 struct HeadsArgs {
   const float* enc;    // (B, D)
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(HD_THREADS) void heads_fwd_kernel(const HeadsArgs a
 #pragma unroll
     for (int o = 0; o < A; ++o) {
       const float n = z[o] - lse;
-      H -= fmaxf(n, HD_F32_MIN) * expf(n);
+      H -= fmaxf(n, RAI_F32_MIN) * expf(n);
       if (o == act) zact = z[o];
       logits_out[b * A + o] = z[o];
     }
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(HD_THREADS) void heads_bwd_rows_kernel(const HeadsA
 #pragma unroll
   for (int o = 0; o < A; ++o) {
     const float n = z[o] - lse;
-    H -= fmaxf(n, HD_F32_MIN) * expf(n);
+    H -= fmaxf(n, RAI_F32_MIN) * expf(n);
   }
   const int act = (int)a.act[b];
   const float gl = d_logp[b], ge = d_ent[b], gv = d_v[b];

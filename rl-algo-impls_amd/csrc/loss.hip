@@ -22,6 +22,7 @@
 // and needs no inter-workgroup protocol.  Per-column accumulators are sized by a
 // compile-time column bound (K = 1 or RAI_MAX_K) so they stay in registers.
 #include "common.h"
+#include "ppo_terms.h"
 
 namespace {
 

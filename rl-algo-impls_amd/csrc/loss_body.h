@@ -1,9 +1,12 @@
 // PPO / A2C loss body (rl_algo_impls/ppo/ppo.py:307-396; rl_algo_impls/a2c/a2c.py:132-158),
 // shared by the standalone loss kernel (loss.hip, rai_ppo_loss) and the fused wide-MLP head + loss
 // kernel (mlp_wide.hip, rai_mlp_wide_forward_loss).  Included inside each file's anonymous
-// namespace.  The reference's rounding sequence is kept by compiling this code without FP
-// contraction wherever it is included (a `#pragma clang fp contract(off)` opens every function
-// with floating-point arithmetic; loss.hip additionally builds with -ffp-contract=off).
+// namespace, after ppo_terms.h at file scope: the clipped surrogate and the value term of a row are that
+// header's, as in every other PPO kernel; here are the advantage moments, the reductions, the kl_cutoff
+// latch, the teacher term, the A2C branch and the stats row.  The reference's rounding sequence is kept by
+// compiling this code without FP contraction wherever it is included (a `#pragma clang fp contract(off)`
+// opens every function with floating-point arithmetic; loss.hip additionally builds with
+// -ffp-contract=off).
 #pragma once
 
 constexpr int LOSS_THREADS = 1024;
@@ -45,18 +48,6 @@ struct AdvNorm {
   float den[RAI_MAX_K];
   float smean, sden;  // scalar (normalize-after-scaling) moments
 };
-
-__device__ __forceinline__ float vf_elem_loss(int fn, float x) {
-#pragma clang fp contract(off)
-  if (fn == 0) return x * x;
-  const float z = fabsf(x);
-  return z < 1.f ? 0.5f * z * z : (z - 0.5f);
-}
-__device__ __forceinline__ float vf_elem_grad(int fn, float x) {  // d loss / d x
-#pragma clang fp contract(off)
-  if (fn == 0) return 2.f * x;
-  return x <= -1.f ? -1.f : (x >= 1.f ? 1.f : x);
-}
 
 // Block sum of NV doubles: wave trees, then NV threads each add the nw wave partials in wave
 // order (fixed order -> deterministic), result broadcast through LDS.  sc holds NV*(nw+1).
@@ -282,7 +273,7 @@ __device__ __forceinline__ void pg_loss_body(const typename loss_args_for<TEACHE
   const AdvNorm nm = nm_s;
 
   // ---- pass 1: forward statistics (ppo.py:326-361, 379-396) --------------------------
-  const float lo = 1.f - hp.clip_range, hi = 1.f + hp.clip_range;
+  // (the rows' gradient weights are known only after the reduction: the terms' d_logp / dv are unused here)
   const float vclip = hp.clip_range_vf;
   const bool vclip_on = ppo && hp.has_clip_range_vf;
   const int vfn = hp.vf_loss_fn;
@@ -292,17 +283,15 @@ __device__ __forceinline__ void pg_loss_body(const typename loss_args_for<TEACHE
   for (int64_t b = tid; b < B; b += NT) {
     const float A = row_adv<KM>(a, hp, nm, b, ADV);
     if (ppo) {
-      const float logratio = NL(b) - OL(b);
-      const float ratio = expf(logratio);
-      const float cr = fminf(fmaxf(ratio, lo), hi);
-      acc[0] += (double)fminf(ratio * A, cr * A);
-      acc[1] += (double)((ratio - 1.f) - logratio);
-      acc[2] += (fabsf(ratio - 1.f) > hp.clip_range) ? 1.0 : 0.0;
+      const PpoSurrogate s = ppo_surrogate(NL(b), OL(b), A, hp.clip_range, 0.f);
+      acc[0] += (double)s.s_min;
+      acc[1] += (double)s.kl_term;
+      acc[2] += (double)s.clipped;
       if constexpr (TEACHER) {
         if (t_on) {  // teacher_kl_loss.py:41-49, in its order of operations
           const float d = TL(b) - NL(b);
           float f = t_unbiased ? (expf(d) - 1.f) - d : 0.5f * (d * d);
-          if (t_is) f = f * ratio;
+          if (t_is) f = f * s.ratio;
           acc[NR - 1] += (double)f;
         }
       }
@@ -312,15 +301,9 @@ __device__ __forceinline__ void pg_loss_body(const typename loss_args_for<TEACHE
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
       if (k < K) {
-        const float v = NV(b, k), R = RET(b, k);
-        float l = vf_elem_loss(vfn, v - R);
-        if (vclip_on) {
-          const float vo = OV(b, k);
-          const float vc = vo + fminf(fmaxf(v - vo, -vclip), vclip);
-          l = fmaxf(l, vf_elem_loss(vfn, vc - R));
-          acc[4 + KM + k] += (fabsf(v - vo) > vclip) ? 1.0 : 0.0;
-        }
-        acc[4 + k] += (double)l;
+        const PpoValue t = ppo_value_term(NV(b, k), RET(b, k), vclip_on ? OV(b, k) : 0.f, vclip_on, vclip, vfn, 0.f);
+        acc[4 + KM + k] += (double)t.clipped;
+        acc[4 + k] += (double)t.loss;
       }
     }
   }
@@ -348,22 +331,13 @@ __device__ __forceinline__ void pg_loss_body(const typename loss_args_for<TEACHE
   for (int64_t b = tid; b < B; b += NT) {
     const float A = row_adv<KM>(a, hp, nm, b, ADV);
     if (ppo) {
-      const float logratio = NL(b) - OL(b);
-      const float ratio = expf(logratio);
-      const float cr = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = ratio * A, s2 = cr * A;
-      float g1, g2;
-      if (s1 < s2) { g1 = g_pi; g2 = 0.f; }
-      else if (s1 > s2) { g1 = 0.f; g2 = g_pi; }
-      else { g1 = g_pi * 0.5f; g2 = g_pi * 0.5f; }
-      const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-      const float d_ratio = g1 * A + (g2 * A) * in_clip;
-      float d_lp = d_ratio * ratio;
+      const PpoSurrogate s = ppo_surrogate(NL(b), OL(b), A, hp.clip_range, g_pi);
+      float d_lp = s.d_logp;
       if constexpr (TEACHER) {
         if (t_on) {  // d(row)/dl in closed form; the ratio carries gradient (not detached)
           const float d = TL(b) - NL(b);
           float dl;
-          if (t_is) dl = t_unbiased ? -(ratio * d) : ratio * (0.5f * (d * d) - d);
+          if (t_is) dl = t_unbiased ? -(s.ratio * d) : s.ratio * (0.5f * (d * d) - d);
           else dl = t_unbiased ? 1.f - expf(d) : -d;
           d_lp += g_t * dl;
         }
@@ -375,24 +349,9 @@ __device__ __forceinline__ void pg_loss_body(const typename loss_args_for<TEACHE
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
       if (k < K) {
-        const float v = NV(b, k), R = RET(b, k);
-        float dv;
-        if (vclip_on) {
-          const float vo = OV(b, k);
-          const float dvo = v - vo;
-          const float vc = vo + fminf(fmaxf(dvo, -vclip), vclip);
-          const float l1 = vf_elem_loss(vfn, v - R);
-          const float l2 = vf_elem_loss(vfn, vc - R);
-          float w1, w2;
-          if (l1 > l2) { w1 = gl[k]; w2 = 0.f; }
-          else if (l1 < l2) { w1 = 0.f; w2 = gl[k]; }
-          else { w1 = gl[k] * 0.5f; w2 = gl[k] * 0.5f; }
-          const float in_vclip = (dvo >= -vclip && dvo <= vclip) ? 1.f : 0.f;
-          dv = w1 * vf_elem_grad(vfn, v - R) + (w2 * vf_elem_grad(vfn, vc - R)) * in_vclip;
-        } else {
-          dv = gl[k] * vf_elem_grad(vfn, v - R);
-        }
-        a.d_values[b * K + k] = dv;
+        const PpoValue t =
+            ppo_value_term(NV(b, k), RET(b, k), vclip_on ? OV(b, k) : 0.f, vclip_on, vclip, vfn, gl[k]);
+        a.d_values[b * K + k] = t.dv;
       }
     }
   }

@@ -14,6 +14,7 @@
 // translation unit shares depend on how many kernels call them, so a kernel added to loss.hip changes
 // the code of the ones already there.  Same launch geometry as rai_ppo_loss.
 #include "common.h"
+#include "ppo_terms.h"
 
 namespace {
 

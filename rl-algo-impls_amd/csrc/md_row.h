@@ -18,7 +18,6 @@
 
 constexpr int MD_MAX_H = RAI_MD_MAX_H, MD_MAX_A = RAI_GRID_MAX_A, MD_MAX_G = RAI_MD_MAX_G;
 constexpr int MD_K = MD_MAX_A / 64;  // logits per lane
-constexpr float MD_F32_MIN = -3.4028234663852886e38f;
 
 struct MdGroups {
   int G, A;
@@ -55,7 +54,7 @@ __device__ __forceinline__ MdGroupStats md_group_stats(const float (&z)[MD_K], c
   for (int k = 0; k < MD_K; ++k) {
     const int a = lane + 64 * k;
     if (a >= lo && a < hi) {
-      m = fmaxf(m, ok[k] ? z[k] : MD_F32_MIN);
+      m = fmaxf(m, ok[k] ? z[k] : RAI_F32_MIN);
       any = any || ok[k];
     }
   }
@@ -85,7 +84,7 @@ __device__ __forceinline__ double md_group_logp(const float (&z)[MD_K], const bo
 #pragma unroll
   for (int k = 0; k < MD_K; ++k) {
     const int a = lane + 64 * k;
-    if (a >= lo && a < hi && a == target) x = ok[k] ? z[k] : MD_F32_MIN;
+    if (a >= lo && a < hi && a == target) x = ok[k] ? z[k] : RAI_F32_MIN;
   }
   x = wave_sum_dpp(x);
   if (!st.any) return 0.0;

@@ -17,7 +17,7 @@
 //       so every layer's accumulator tile is the next layer's B operand in place (no data movement on
 //       the forward / backward chain; the A operands are W2 permutations staged once in LDS);
 //       the output layer and its backward as lane-group sums (v_permlane16/32_swap) in the epilogue;
-//       the per-row loss and its gradient w.r.t. the head outputs (the arithmetic of mlp_ppo.hip);
+//       the per-row loss and its gradient w.r.t. the head outputs (a contracted copy of ppo_terms.h);
 //       dW2 += dZ2^T H1 and [dW1 | db1] += dZ1^T [x | 1] on MFMA with the rows as the reduction axis
 //       (dZ2, H1, dZ1 transposed through a per-wave LDS tile; the x operand is loaded transposed);
 //       dW3, db2, db3 as per-lane partial sums.
@@ -55,7 +55,6 @@ constexpr int LB_TS = 24;             // transpose-tile row stride (floats): con
 constexpr int LB_PSTRIDE = 4612;      // >= actor block 64*4+64+64*64+64+2*64+2 = 4610, multiple of 4
 constexpr int LB_MOMP = 64;           // advantage-moment partial chunks per minibatch
 constexpr int LB_RED_NT = 256;        // reduce kernel: 64 parameters x 4 partial quarters per block
-constexpr float F32_MIN = -3.4028234663852886e38f;
 
 struct LbSmem {
   float w2f[4][4][64][4];  // forward A operands   [m2][blk][lane][i] = W2[16 m2 + j][16 blk + 4 g + i]
@@ -375,7 +374,9 @@ __device__ __forceinline__ void lb_net(const LbArgs& a, LbSmem& S, int wgn) {
       zo[o] = lb_sum_groups((p[0] + p[1]) + (p[2] + p[3])) + S.b3[o];
     }
   };
-  // loss per row (ppo.py:326-371; the min/max tie rules of loss.hip): gradient w.r.t. the outputs
+  // loss per row (ppo.py:326-371): gradient w.r.t. the outputs.  The reference form of the surrogate and
+  // value terms, with the min / max tie rules, is ppo_terms.h; this copy stays because this kernel keeps
+  // FP contraction on and uses the fast lb_exp / lb_log (fp32 tolerance, not bit equality; see the top).
   auto loss = [&](const LbIn& in, const float (&zo)[OUT], float& d0, float& d1) {
     const bool valid = in.valid;
     const bool count = valid && g == 0;
@@ -386,7 +387,7 @@ __device__ __forceinline__ void lb_net(const LbArgs& a, LbSmem& S, int wgn) {
       const float lse = mx + lb_log(lb_exp(z0 - mx) + lb_exp(z1 - mx));
       const float n0 = z0 - lse, n1 = z1 - lse;
       const float p0 = lb_exp(n0), p1 = lb_exp(n1);
-      const float H = -(fmaxf(n0, F32_MIN) * p0) - fmaxf(n1, F32_MIN) * p1;
+      const float H = -(fmaxf(n0, RAI_F32_MIN) * p0) - fmaxf(n1, RAI_F32_MIN) * p1;
       const bool a1 = in.act == 1;
       const float logp = a1 ? n1 : n0;
       const float A = (in.u1 - amean) / aden;

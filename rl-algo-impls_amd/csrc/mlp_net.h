@@ -274,7 +274,7 @@ __device__ __forceinline__ void mlp_net(const MlpArgs& a, Smem<INP, OUTP>& S) {
       lds_barrier();
       STAMP(2);
       // ---- L: per-row loss gradient w.r.t. the head outputs (ppo.py:326-371 semantics; autograd
-      //      tie rules of min/max and closed-interval clamp, as loss.hip) ---------------------------
+      //      tie rules of min/max and closed-interval clamp: ppo_terms.h) ---------------------------
       {
         RELANE();
         const int s = tid - c * CH;

@@ -21,9 +21,10 @@
 //   mlp_net.h        one CU per network: shapes up to (8, 8) (RAI_MLP_LAYOUT=chunk: CartPole too)
 //   mlp_mc_common.h  what they share: the small device helpers, clip coefficient, stat rows, weight
 //                    layout, exchange region, weight / moment load and write-back
-//   ppo_row_loss.h   the per-row loss and its gradient
+//   ppo_row_loss.h   the per-row loss and its gradient (the surrogate and value terms: ppo_terms.h)
 #include "common.h"
 #include "internal.h"
+#include "ppo_terms.h"
 
 #include <algorithm>
 #include <cstdlib>

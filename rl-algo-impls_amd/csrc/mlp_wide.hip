@@ -26,6 +26,7 @@
 // All sums run in a fixed order: deterministic; fp32 like the reference (different association
 // than hipBLASLt's, so parity is to fp32 tolerance, tests/test_gpu_trainer.py).
 #include "common.h"
+#include "ppo_terms.h"
 
 namespace {
 
@@ -288,7 +289,7 @@ __device__ __forceinline__ void wide_head_body(const WideArgs& a) {
       float h = 0.f;
       for (int o = 0; o < A; ++o) {
         const float l = outs[b][o] - lse;
-        h -= fmaxf(l, -3.4028234663852886e38f) * expf(l);
+        h -= fmaxf(l, RAI_F32_MIN) * expf(l);
       }
       a.logp[b] = outs[b][ai >= 0 && ai < A ? ai : 0] - lse;
       a.ent[b] = h;

@@ -37,6 +37,7 @@
 // (v_mfma_f32_16x16x4f32), Adam with the hardware sqrt / rcp (as the CartPole epoch kernel); parity
 // to fp32 tolerance against the per-minibatch path and the reference (tests/test_gpu_trainer.py).
 #include "common.h"
+#include "ppo_terms.h"
 
 namespace {
 
@@ -176,18 +177,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t we_rsrc(const void* p, int64_t
 }
 __device__ __forceinline__ float we_act(int act, float z) { return act ? fmaxf(z, 0.f) : tanhf(z); }
 __device__ __forceinline__ float we_actd(int act, float h) { return act ? (h > 0.f ? 1.f : 0.f) : (1.f - h * h); }
-
-__device__ __forceinline__ float we_vf_loss(int fn, float x) {
-#pragma clang fp contract(off)
-  if (fn == 0) return x * x;
-  const float z = fabsf(x);
-  return z < 1.f ? 0.5f * z * z : (z - 0.5f);
-}
-__device__ __forceinline__ float we_vf_grad(int fn, float x) {
-#pragma clang fp contract(off)
-  if (fn == 0) return 2.f * x;
-  return x <= -1.f ? -1.f : (x >= 1.f ? 1.f : x);
-}
 
 // 16 x 16 tile of  Rows[16 tiles rows][k] . Cols[16][k]^T  over k in [0, H) (LDS, ld WE_HP): lane
 // group g takes the contiguous quarter [g H/4, (g+1) H/4), four accumulator chains (one per f4
@@ -909,8 +898,8 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
     if (HEAD == 1 && net == 0) {
       // Gaussian actor: every wave, 16 rows each, four lanes per row (lane & 3 = dimension pair dp: dims
       // 2 dp, 2 dp + 1).  The log-prob's eight per-dimension terms are gathered across the quad and summed
-      // in dimension order (the one-wave form's order), so every lane of the quad forms the identical row
-      // values; each lane then writes the loss gradient of its two dimensions.
+      // in dimension order (0 to 7, one chain), so every lane of the quad forms the identical row values;
+      // each lane then writes the loss gradient of its two dimensions.
 #pragma clang fp contract(off)
       const int rq = lane >> 2, dp = lane & 3;
       const int r = 16 * w + rq;
@@ -951,18 +940,8 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
       const float A = c_adv;  // normalized per minibatch by we_pack_kernel before the epoch
       const float ent = S.entc;
       const float invB = mb + 1 < nmb ? invB_full : invB_last;
-      const float logratio = lp - c_lpold;
-      const float ratio = expf(logratio);
-      const float lo = 1.f - hp.clip_range, hi = 1.f + hp.clip_range;
-      const float cr = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = ratio * A, s2 = cr * A;
-      const float g_pi = -invB;
-      float g1, g2;
-      if (s1 < s2) { g1 = g_pi; g2 = 0.f; }
-      else if (s1 > s2) { g1 = 0.f; g2 = g_pi; }
-      else { g1 = g_pi * 0.5f; g2 = g_pi * 0.5f; }
-      const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-      const float d_logp = valid ? (g1 * A + (g2 * A) * in_clip) * ratio : 0.f;
+      const PpoSurrogate s = ppo_surrogate(lp, c_lpold, A, hp.clip_range, -invB);
+      const float d_logp = valid ? s.d_logp : 0.f;
       const float d_ent = valid ? (mb + 1 < nmb ? dent_full : dent_last) : 0.f;
       float dd[2], dlv[2];
 #pragma unroll
@@ -975,19 +954,18 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
       *reinterpret_cast<float2*>(&S.dOut[r][o0]) = float2{dd[0], dd[1]};
       *reinterpret_cast<float2*>(&S.dls[r][o0]) = float2{dlv[0], dlv[1]};
       if (dp == 0) {
-        S.st[0][r] = valid ? (double)fminf(s1, s2) : 0.0;
-        S.st[1][r] = valid ? (double)((ratio - 1.f) - logratio) : 0.0;
-        S.st[2][r] = valid ? ((fabsf(ratio - 1.f) > hp.clip_range) ? 1.0 : 0.0) : 0.0;
+        S.st[0][r] = valid ? (double)s.s_min : 0.0;
+        S.st[1][r] = valid ? (double)s.kl_term : 0.0;
+        S.st[2][r] = valid ? (double)s.clipped : 0.0;
         S.st[3][r] = valid ? (double)ent : 0.0;
       }
       WSTAMP(7);
-    } else if (w == 0) {
+    } else if (w == 0) {  // the Categorical actor (the Gaussian one took the branch above) and the critic
       const int r = lane;
       const bool valid = r < rows;
       const f4* lin = reinterpret_cast<const f4*>(&S.Xl[WE_B * WE_INMAX + r * WE_LIN]);
-      const f4 l0 = lin[0], l1 = lin[1], l2 = lin[2];
+      const f4 l0 = lin[0], l1 = lin[1];
       const float c_adv = l0.x, c_lpold = l0.y, c_ret = l0.z, c_vold = l0.w;
-      const float c_act[WE_OUTM] = {l1.x, l1.y, l1.z, l1.w, l2.x, l2.y, l2.z, l2.w};
       const int64_t c_ai = __float_as_int(l1.x);
       // head outputs: the four waves' slice sums in order, + b3 (16-B LDS reads; entries o >= O are
       // zero throughout -- partials, W3 columns and b3 padding -- so no per-dimension branches)
@@ -1005,140 +983,74 @@ __device__ void we_epoch(const WeArgs& a, WeSmem& S, const int net, const int j)
           out[4 + o] = oh[o];
         }
       }
-      float dout[WE_OUTM], dl[WE_OUTM];
+      float dout[WE_OUTM];
 #pragma unroll
-      for (int o = 0; o < WE_OUTM; ++o) dout[o] = dl[o] = 0.f;
+      for (int o = 0; o < WE_OUTM; ++o) dout[o] = 0.f;
       // statistics: [0] sum min(s1, s2) | loss, [1] sum kl | vclipped, [2] clipped, [3] entropy
       double st[4] = {0.0, 0.0, 0.0, 0.0};  // per row; summed by side_d
       const bool full = mb + 1 < nmb;  // the loss's per-step divides, formed before the loop
       const float invB = full ? invB_full : invB_last;
       if (net == 0) {
 #pragma clang fp contract(off)
-        const float A = c_adv;  // normalized per minibatch by we_adv_norm_kernel before the epoch
-        float lp = 0.f, ent = 0.f;  // log-prob of the action, entropy (summed over dims)
-        // Normal.log_prob's divisions by var and 2 var as products with the per-step reciprocal
-        // (within an ulp of torch's quotients)
-        float ginv[WE_OUTM];
-        if (HEAD == 1) {
+        const float A = c_adv;  // normalized per minibatch by we_pack_kernel before the epoch
+        const int64_t ai = c_ai;
+        float mx = out[0];
 #pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o) ginv[o] = S.ginv[o];
+        for (int o = 1; o < WE_OUTM; ++o)
+          if (o < O) mx = fmaxf(mx, out[o]);
+        float se = 0.f;
 #pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o) {  // dimensions o >= O masked (no uniform branches)
-            const float xo = c_act[o] - out[o];
-            const float term = -(xo * xo) * (0.5f * ginv[o]) - S.glsc[o] - 0.91893853320467274f;
-            lp += o < O ? term : 0.f;
+        for (int o = 0; o < WE_OUTM; ++o)
+          if (o < O) se += expf(out[o] - mx);
+        const float lse = mx + logf(se);
+        float ent = 0.f;  // the statistic: log p clamped at finfo.min, as torch's Categorical.entropy
+        float za = out[0];
+#pragma unroll
+        for (int o = 0; o < WE_OUTM; ++o)
+          if (o < O) {
+            const float l = out[o] - lse;
+            ent -= fmaxf(l, RAI_F32_MIN) * expf(l);
+            if (o == (ai >= 0 && ai < O ? ai : 0)) za = out[o];
           }
-          ent = S.entc;
-        } else {
-          const int64_t ai = c_ai;
-          float mx = out[0];
-#pragma unroll
-          for (int o = 1; o < WE_OUTM; ++o)
-            if (o < O) mx = fmaxf(mx, out[o]);
-          float se = 0.f;
-#pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o)
-            if (o < O) se += expf(out[o] - mx);
-          const float lse = mx + logf(se);
-          float h = 0.f;
-          float za = out[0];
-#pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o)
-            if (o < O) {
-              const float l = out[o] - lse;
-              h -= fmaxf(l, -3.4028234663852886e38f) * expf(l);
-              if (o == (ai >= 0 && ai < O ? ai : 0)) za = out[o];
-            }
-          lp = za - lse;
-          ent = h;
-        }
-        const float logratio = lp - c_lpold;
-        const float ratio = expf(logratio);
-        const float lo = 1.f - hp.clip_range, hi = 1.f + hp.clip_range;
-        const float cr = fminf(fmaxf(ratio, lo), hi);
-        const float s1 = ratio * A, s2 = cr * A;
-        const float g_pi = -invB;
-        float g1, g2;
-        if (s1 < s2) { g1 = g_pi; g2 = 0.f; }
-        else if (s1 > s2) { g1 = 0.f; g2 = g_pi; }
-        else { g1 = g_pi * 0.5f; g2 = g_pi * 0.5f; }
-        const float in_clip = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-        const float d_logp = valid ? (g1 * A + (g2 * A) * in_clip) * ratio : 0.f;
+        const PpoSurrogate s = ppo_surrogate(za - lse, c_lpold, A, hp.clip_range, -invB);
+        const float d_logp = valid ? s.d_logp : 0.f;
         const float d_ent = valid ? (full ? dent_full : dent_last) : 0.f;
-        if (HEAD == 1) {
+        float h = 0.f;  // the entropy in the gradient: no clamp
 #pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o) {
-            const float xo = c_act[o] - out[o];
-            const bool on = o < O;
-            dout[o] = on ? d_logp * (xo * ginv[o]) : 0.f;
-            dl[o] = on ? d_logp * ((xo * xo) * ginv[o] - 1.f) + d_ent : 0.f;
+        for (int o = 0; o < WE_OUTM; ++o)
+          if (o < O) {
+            const float l = out[o] - lse;
+            h -= l * expf(l);
           }
-        } else {
-          const int64_t ai = c_ai;
-          float mx = out[0];
 #pragma unroll
-          for (int o = 1; o < WE_OUTM; ++o)
-            if (o < O) mx = fmaxf(mx, out[o]);
-          float se = 0.f;
-#pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o)
-            if (o < O) se += expf(out[o] - mx);
-          const float lse = mx + logf(se);
-          float h = 0.f;
-#pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o)
-            if (o < O) {
-              const float l = out[o] - lse;
-              h -= l * expf(l);
-            }
-#pragma unroll
-          for (int o = 0; o < WE_OUTM; ++o)
-            if (o < O) {
-              const float l = out[o] - lse, p = expf(l);
-              dout[o] = d_logp * ((o == ai ? 1.f : 0.f) - p) - d_ent * p * (l + h);
-            }
-        }
+        for (int o = 0; o < WE_OUTM; ++o)
+          if (o < O) {
+            const float l = out[o] - lse, p = expf(l);
+            dout[o] = d_logp * ((o == ai ? 1.f : 0.f) - p) - d_ent * p * (l + h);
+          }
         if (valid) {
-          st[0] = (double)fminf(s1, s2);
-          st[1] = (double)((ratio - 1.f) - logratio);
-          st[2] = (fabsf(ratio - 1.f) > hp.clip_range) ? 1.0 : 0.0;
+          st[0] = (double)s.s_min;
+          st[1] = (double)s.kl_term;
+          st[2] = (double)s.clipped;
           st[3] = (double)ent;
         }
       } else {
 #pragma clang fp contract(off)
-        const float v = out[0], R = c_ret;
         const float halve = hp.ppo2_vf_coef_halving ? 0.5f : 1.f;
         const float gl = (hp.vf_coef[0] * halve) * invB;
-        const int vfn = hp.vf_loss_fn;
-        float l = we_vf_loss(vfn, v - R), dv;
-        float vcf = 0.f;
-        if (hp.has_clip_range_vf) {
-          const float vc_ = hp.clip_range_vf, vo = c_vold;
-          const float dvo = v - vo;
-          const float vcl = vo + fminf(fmaxf(dvo, -vc_), vc_);
-          const float l2 = we_vf_loss(vfn, vcl - R);
-          float w1, w2;
-          if (l > l2) { w1 = gl; w2 = 0.f; }
-          else if (l < l2) { w1 = 0.f; w2 = gl; }
-          else { w1 = gl * 0.5f; w2 = gl * 0.5f; }
-          const float inv = (dvo >= -vc_ && dvo <= vc_) ? 1.f : 0.f;
-          dv = w1 * we_vf_grad(vfn, v - R) + (w2 * we_vf_grad(vfn, vcl - R)) * inv;
-          vcf = (fabsf(v - vo) > vc_) ? 1.f : 0.f;
-          l = fmaxf(l, l2);
-        } else {
-          dv = gl * we_vf_grad(vfn, v - R);
-        }
-        dout[0] = valid ? dv : 0.f;
+        const PpoValue t = ppo_value_term(out[0], c_ret, c_vold, hp.has_clip_range_vf != 0, hp.clip_range_vf,
+                                          hp.vf_loss_fn, gl);
+        dout[0] = valid ? t.dv : 0.f;
         if (valid) {
-          st[0] = (double)l;
-          st[1] = (double)vcf;
+          st[0] = (double)t.loss;
+          st[1] = (double)t.clipped;
         }
       }
       WSTAMP(7);
       *reinterpret_cast<f4*>(&S.dOut[r][0]) = f4{dout[0], dout[1], dout[2], dout[3]};
       *reinterpret_cast<f4*>(&S.dOut[r][4]) = f4{dout[4], dout[5], dout[6], dout[7]};
-      *reinterpret_cast<f4*>(&S.dls[r][0]) = f4{dl[0], dl[1], dl[2], dl[3]};
-      *reinterpret_cast<f4*>(&S.dls[r][4]) = f4{dl[4], dl[5], dl[6], dl[7]};
+      *reinterpret_cast<f4*>(&S.dls[r][0]) = f4{0.f, 0.f, 0.f, 0.f};  // no log_std on these rows
+      *reinterpret_cast<f4*>(&S.dls[r][4]) = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < 4; ++i) S.st[i][r] = st[i];
     }

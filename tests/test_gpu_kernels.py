@@ -254,6 +254,34 @@ def test_loss_kernel_tie_semantics():
     np.testing.assert_allclose(d_lp.cpu().numpy(), t.grad.numpy(), rtol=1e-6)
 
 
+@pytest.mark.parametrize("vf_loss_fn", ["mse_loss", "huber_loss"])
+def test_loss_kernel_value_tie_semantics(vf_loss_fn):
+    """new_values == old_values exactly, so the clipped value equals the value and l == l2 on every row:
+    torch.max splits the tie 1/2 : 1/2 and the clamp passes its half (the move, 0, is inside the closed
+    interval), and so must the kernel.  Returns over [-2, 2] put |v - R| on both sides of Huber's knee."""
+    B, vclip, vf_coef = 8, 0.2, 0.5
+    v = np.array([0.3, -0.6, 0.2, 0.1, -0.1, 0.5, -0.3, 0.4], np.float32)
+    ret = np.linspace(-2.0, 2.0, B).astype(np.float32)
+    assert (np.abs(v - ret) < 1).any() and (np.abs(v - ret) > 1).any()
+    zeros = np.zeros(B, np.float32)
+    kw = dict(normalize_advantage=False, clip_range_vf=vclip, vf_coef=vf_coef, vf_loss_fn=vf_loss_fn)
+    blocks = DeviceBlocks(DEV)
+    blocks.upload(_kw_to_hparams(kw, 1), 0)
+    _, _, d_v = launch_loss(blocks, dev(zeros), dev(zeros), dev(v), dev(zeros), dev(v), dev(zeros), dev(ret), 1)
+    # autograd reference
+    t = torch.from_numpy(v).clone().requires_grad_(True)
+    old, R = torch.from_numpy(v), torch.from_numpy(ret)
+    if vf_loss_fn == "huber_loss":
+        vf = lambda a, b: torch.nn.functional.smooth_l1_loss(a, b, reduction="none", beta=1.0)
+    else:
+        vf = lambda a, b: (a - b) ** 2
+    l = vf(t, R)
+    l2 = vf(old + torch.clamp(t - old, -vclip, vclip), R)
+    assert torch.equal(l.detach(), l2.detach())
+    (vf_coef * torch.max(l, l2).mean()).backward()
+    np.testing.assert_allclose(d_v.cpu().numpy().reshape(B), t.grad.numpy(), rtol=1e-6)
+
+
 # ---------------------------------------------------------------- optimizer -----------
 def test_clip_adam_matches_torch_over_steps():
     from rl_algo_impls_amd.optim import FlatOptimizer, FlatParams

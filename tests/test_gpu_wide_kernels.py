@@ -65,6 +65,8 @@ def cid(c) -> str:
         s += f"-vclip{c.vclip}"
     if getattr(c, "ent_coef", None) is not None:
         s += f"-ent{c.ent_coef}"
+    if getattr(c, "vf", "mse_loss") != "mse_loss":
+        s += "-huber"
     return s
 
 
@@ -398,6 +400,10 @@ def test_case_table_covers_the_required_combinations():
     assert all(has(head=h, act=a, acc=m) for h in (G, K) for a in ("tanh", "relu") for m in (0, 1))
     assert not has(out=1, head=K)  # a one-action Categorical is degenerate
     assert len({cid(c) for c in CASES}) == len(CASES)
+    # the whole-epoch cases: both value-loss forms, Huber with and without value clipping
+    assert {c.vf for c in ECASES} == {"mse_loss", "huber_loss"}
+    assert {c.vclip is not None for c in ECASES if c.vf == "huber_loss"} == {True, False}
+    assert len({cid(c) for c in ECASES}) == len(ECASES)
 
 
 @pytest.mark.gpu
@@ -550,7 +556,7 @@ def test_forward_loss_equals_forward_then_ppo_loss(B, head, vclip, ent_coef):
 # ---------------------------------------------------------------------------------------------
 # 3. the whole-epoch kernel's gradient, from Adam's first moment after one step
 # ---------------------------------------------------------------------------------------------
-ECase = namedtuple("ECase", "H in_dim out B head act vclip ent_coef pshift seed", defaults=(0, 0))
+ECase = namedtuple("ECase", "H in_dim out B head act vclip ent_coef pshift seed vf", defaults=(0, 0, "mse_loss"))
 ECASES = [
     ECase(256, 17, 6, 64, G, "relu", None, 0.01),
     ECase(256, 17, 6, 50, G, "tanh", 0.2, 0.0),
@@ -568,9 +574,13 @@ ECASES = [
     ECase(256, 17, 8, 64, K, "relu", 0.2, 0.01),
     ECase(64, 17, 1, 50, G, "tanh", 0.2, 0.01, pshift=1),
     ECase(256, 1, 6, 16, K, "relu", None, 0.01),
+    # the critic's Huber branch (vf_loss_fn = 1), with and without value clipping
+    ECase(64, 3, 6, 16, G, "tanh", 0.2, 0.01, vf="huber_loss"),
+    ECase(256, 17, 8, 50, K, "relu", None, 0.0, vf="huber_loss"),
 ]
 # one seed per case, searched on the CPU upwards from 3000 + 100 * index for epoch_conditions(margin=4e-4)
-ESEEDS = [3000, 3100, 3200, 3301, 3400, 3500, 3600, 3702, 3802, 3900, 4000, 4102, 4200, 4302, 4400, 4500]
+# (which, for a Huber case, also asks for rows on both sides of |v - R| = 1 in the float64 reference)
+ESEEDS = [3000, 3100, 3200, 3301, 3400, 3500, 3600, 3702, 3802, 3900, 4000, 4102, 4200, 4302, 4400, 4500, 4600, 4700]
 assert len(ESEEDS) == len(ECASES)
 ECASES = [c._replace(seed=s) for c, s in zip(ECASES, ESEEDS)]
 CLIP, VF_COEF, BETA1 = 0.2, 0.5, 0.9
@@ -590,8 +600,8 @@ def epoch_inputs(c):
 
 def ppo_ref(c, params, obs, actions, old_logp, old_v, adv, ret, dtype, device="cpu"):
     """rl_algo_impls/ppo/ppo.py:290-377 for K = 1: minibatch-normalized advantages, the clipped
-    surrogate, the value MSE (optionally clipped around old_v), the entropy term; gradients by
-    autograd.  Returns the gradients, their norm, stats columns 0..5 (column 0 without the value term,
+    surrogate, the value loss (MSE, or Huber = smooth_l1 with beta 1: 0.5 z^2 for |z| < 1, else
+    |z| - 0.5; optionally clipped around old_v), the entropy term; gradients by autograd.  Returns the gradients, their norm, stats columns 0..5 (column 0 without the value term,
     as the kernel writes it) and the ratios / value moves for the conditions."""
     p = [t.requires_grad_(True) for t in cast(params, dtype, device)]
     obs, actions, old_logp, old_v, adv, ret = cast([obs, actions, old_logp, old_v, adv, ret], dtype, device)
@@ -600,10 +610,14 @@ def ppo_ref(c, params, obs, actions, old_logp, old_v, adv, ret, dtype, device="c
     logratio = logp - old_logp
     ratio = logratio.exp()
     pi_loss = -torch.min(ratio * A, ratio.clamp(1 - CLIP, 1 + CLIP) * A).mean()
-    v_loss = (v - ret) ** 2
+    if c.vf == "huber_loss":
+        vf = lambda z: torch.where(z.abs() < 1, 0.5 * z * z, z.abs() - 0.5)
+    else:
+        vf = lambda z: z ** 2
+    v_loss = vf(v - ret)
     if c.vclip is not None:
         v_cl = old_v + (v - old_v).clamp(-c.vclip, c.vclip)
-        v_loss = torch.max(v_loss, (v_cl - ret) ** 2)
+        v_loss = torch.max(v_loss, vf(v_cl - ret))
     v_loss = v_loss.mean()
     ent_loss = -ent.mean()
     grads = torch.autograd.grad(pi_loss + c.ent_coef * ent_loss + VF_COEF * v_loss, p)
@@ -613,7 +627,8 @@ def ppo_ref(c, params, obs, actions, old_logp, old_v, adv, ret, dtype, device="c
                          det(((ratio - 1) - logratio).mean()),
                          det(((ratio - 1).abs() > CLIP).to(dtype).mean()), det(v_loss)])
     norm = torch.sqrt(sum((g_ ** 2).sum() for g_ in grads))
-    return SimpleNamespace(grads=grads, stats=stats, norm=norm, ratio=det(ratio), dv=det(v - old_v))
+    return SimpleNamespace(grads=grads, stats=stats, norm=norm, ratio=det(ratio), dv=det(v - old_v),
+                           verr=det(v - ret))
 
 
 def epoch_conditions(c, ref, zs, margin=1e-4):
@@ -627,6 +642,8 @@ def epoch_conditions(c, ref, zs, margin=1e-4):
     clipped = (ref.ratio - 1).abs() > CLIP
     if not (bool(clipped.any()) and bool((~clipped).any())):
         return "the rows do not exercise both clip branches"
+    if c.vf == "huber_loss" and not (bool((ref.verr.abs() < 1).any()) and bool((ref.verr.abs() > 1).any())):
+        return "the rows do not lie on both sides of |v - R| = 1"
     return None
 
 
@@ -666,7 +683,7 @@ def test_epoch_gradient_from_first_moment(c):
     from rl_algo_impls_amd.optim import struct_to_device
 
     hp = struct_to_device(make_hparams(loss_kind=0, K=1, clip_range=CLIP, clip_range_vf=c.vclip, ent_coef=c.ent_coef,
-                                       vf_coef=VF_COEF, normalize_advantage=True), DEV)
+                                       vf_coef=VF_COEF, normalize_advantage=True, vf_loss_fn=c.vf), DEV)
     ohp = struct_to_device(_lib.OptimHparams(lr=3e-4, beta1=BETA1, beta2=0.999, eps=1e-7, alpha=0.99,
                                              max_grad_norm=1e30, kind=0, beta1_d=BETA1, beta2_d=0.999), DEV)
     state = struct_to_device(_lib.TrainState(opt_step=0, stat_index=0, pi_coef_zero=0, norm_index=0), DEV)
