@@ -8,18 +8,27 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 
+def rendezvous():
+    """What the spawning test hands its ranks as `port`: the path of a fresh rendezvous file in a new
+    temporary directory.  (A TCP port found by bind-to-0-and-close is free only until some other process
+    takes it: rank 0 then dies with EADDRINUSE seconds later, once it has imported torch.)"""
+    import tempfile
+
+    return os.path.join(tempfile.mkdtemp(prefix="rai-dp-rendezvous-"), "store")
+
+
 def _init(rank, world, port, backend="gloo"):
+    """port: the rendezvous() file path the spawning test made."""
     import torch
     import torch.distributed as dist
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
+    method = "file://" + port
     if backend == "nccl":
         dev = torch.device("cuda", 0)
         torch.cuda.set_device(dev)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+        dist.init_process_group("nccl", init_method=method, rank=rank, world_size=world, device_id=dev)
     else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        dist.init_process_group("gloo", init_method=method, rank=rank, world_size=world)
 
 
 def moments_worker(rank, world, port, q):

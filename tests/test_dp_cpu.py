@@ -1,16 +1,7 @@
 """Data-parallel host logic on CPU with the gloo backend, world_size=2."""
 import multiprocessing as mp
-import socket
 
 import numpy as np
-
-
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_global_advantage_moments_world2():
@@ -18,7 +9,7 @@ def test_global_advantage_moments_world2():
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.moments_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -39,7 +30,7 @@ def test_dp_batch_rules_world2():
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.batch_rule_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -65,7 +56,7 @@ def test_replicated_update_rollout_assembly_world2():
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.replicated_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

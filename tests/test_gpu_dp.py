@@ -1,7 +1,6 @@
 """Data-parallel PPO update with real kernels: 2 ranks (gloo, both on cuda:0) vs the
 single-process fused update over the equivalent global minibatches."""
 import multiprocessing as mp
-import socket
 
 import numpy as np
 import pytest
@@ -10,12 +9,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+@pytest.fixture(autouse=True)
+def _no_rank_outlives_its_test():
+    """A test that fails because one rank died leaves the other ranks waiting for it in a collective; the
+    interpreter would then join them at exit, for as long as their timeouts last.  End them here."""
+    yield
+    for p in mp.active_children():
+        p.terminate()
+        p.join(timeout=30)
+        if p.is_alive():
+            p.kill()
 
 
 @pytest.mark.parametrize("dp_batch", ["global", "per-rank"])
@@ -47,7 +50,7 @@ def _fused_dp_world2_check(dp_batch="per-rank", inject_fail_rank=None):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.fused_dp_worker, args=(r, 2, port, q, "gloo", dp_batch, inject_fail_rank))
              for r in range(2)]
     for p in procs:
@@ -109,7 +112,7 @@ def _run_world1(backend):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=dp_worker.fused_dp_worker, args=(0, 1, _port(), q, backend))
+    p = ctx.Process(target=dp_worker.fused_dp_worker, args=(0, 1, dp_worker.rendezvous(), q, backend))
     p.start()
     deadline = time.time() + 240
     while True:
@@ -152,7 +155,7 @@ def test_wide_mlp_dp_world2_matches_single_process_global_minibatches(dp_batch):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.wide_dp_worker, args=(r, 2, port, q, dp_batch)) for r in range(2)]
     for p in procs:
         p.start()
@@ -198,7 +201,7 @@ def test_multicritic_dp_world2_matches_single_process_global_minibatches(after):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.mc_dp_worker, args=(r, 2, port, q, after)) for r in range(2)]
     for p in procs:
         p.start()
@@ -245,7 +248,7 @@ def test_nature_cnn_bucketed_allreduce_world1_matches_single_process():
     out = {}
     for mode in ("buckets", "flat", "single"):
         q = ctx.Queue()
-        p = ctx.Process(target=dp_worker.cnn_dp_worker, args=(0, 1, _port(), q, mode))
+        p = ctx.Process(target=dp_worker.cnn_dp_worker, args=(0, 1, dp_worker.rendezvous(), q, mode))
         p.start()
         deadline = time.time() + 240
         while True:
@@ -284,7 +287,7 @@ def test_env_partition_split_world2_matches_single_process_c2(world):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.split_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -337,7 +340,7 @@ def test_replicated_update_matches_single_process_bitwise(kind, world):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.replicated_gpu_worker, args=(r, world, port, q, kind))
              for r in range(world)]
     for p in procs:
@@ -388,7 +391,7 @@ def test_wide_epoch_xdp_world2_matches_single_process_global_minibatches(hidden,
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.wide_epoch_xdp_worker, args=(r, 2, port, q, hidden, rows, n)) for r in range(2)]
     for p in procs:
         p.start()
@@ -461,7 +464,7 @@ def test_scaled_batch_policy_dp_world2_matches_single_process(xdp, world):
     rows, n = 512, 2048  # > 256 rows per rank: the large-minibatch kernels at every world size
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.large_dp_worker, args=(r, world, port, q, rows, n, xdp))
              for r in range(world)]
     for p in procs:

@@ -3,7 +3,6 @@ A16 HyperparamTransitions, A17 RunningMeanStd / Normalize* wrappers (incl. the w
 cross-rank merge), A18 EpisodeStatsWriter.  CPU only."""
 import json
 import multiprocessing as mp
-import socket
 from types import SimpleNamespace
 
 import numpy as np
@@ -159,21 +158,13 @@ def test_episode_stats_writer_matches_reference(sched):
     np.testing.assert_allclose([v for _, v in rec.scalars], [v for _, v in es["scalars"]], rtol=1e-12)
 
 
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_normalize_cross_rank_merge_world2(host):
     """Two ranks holding 3 + 5 of the 8 envs normalise like one process holding all 8."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _port()
     import dp_worker
 
+    port = dp_worker.rendezvous()
     procs = [ctx.Process(target=dp_worker.rms_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
