@@ -159,6 +159,33 @@ int rai_bias_gelu_fwd(const float* x, const float* b, int64_t rows, int32_t C, f
 int rai_bias_gelu_bwd(const float* dy, const float* x, const float* b, int64_t rows, int32_t C, float* dx,
                       void* stream);
 
+/* Channel layer norm of the squeeze-U-Net with `normalization: layer` (ChannelLayerNorm2d,
+ * rl_algo_impls/shared/module/channel_layer_norm.py, after every backbone and critic convolution:
+ * squeeze_unet.py, double_cone.py:SEResidualBlock, backbone_actor_critic.py), fused with the
+ * convolution's bias and the GELU that follows it.  NHWC fp32 activations viewed (rows, C),
+ * rows = B*H*W, C fastest; x is the bias-free convolution output.
+ *   forward (one launch):  z = x + bias[c];  mean = sum_c z / C;  var = sum_c (z - mean)^2 / (C - 1)
+ *     (torch's default unbiased variance, computed from the centred values);  rstd = 1 / sqrt(var + eps);
+ *     y = gamma[c] * (z - mean) * rstd + beta[c];  out = gelu ? GELU(y) : y (exact erf GELU);
+ *     stats (rows, 2) keeps (mean, rstd) for the backward.
+ *   backward (two launches):  dy = dout * (gelu ? GELU'(y) : 1);  g = dy * gamma;  xh = (z - mean) * rstd;
+ *     dx = rstd * (g - mean_c(g) - xh * sum_c(g * xh) / (C - 1));
+ *     dgamma[c] = sum_rows dy * xh;  dbeta[c] = sum_rows dy;  dbias[c] = sum_rows dx  (written, not
+ *     accumulated).  The column sums run in an order fixed by (rows, C): per-workgroup partials in
+ *     workspace, summed by the second launch; two calls on the same inputs give the same bits.
+ * C % 4 == 0, C / 4 a power of two, 16 <= C <= RAI_CLN_MAX_C (C in {16, 32, 64, 128, 256}), else
+ * RAI_E_SHAPE.  rows == 0: RAI_OK, and the backward zeroes dgamma, dbeta, dbias.  bias, gamma, beta
+ * need 4-byte alignment only (views into the flat parameter buffer); x, out, dout, dx and workspace
+ * must be 16-byte aligned (RAI_E_WORKSPACE otherwise).  workspace: at least
+ * rai_chan_ln_workspace_bytes(C) bytes, no initialisation needed; one per concurrently running launch. */
+#define RAI_CLN_MAX_C 256
+int64_t rai_chan_ln_workspace_bytes(int32_t C);
+int rai_chan_ln_fwd(const float* x, const float* bias, const float* gamma, const float* beta, int64_t rows,
+                    int32_t C, float eps, int32_t gelu, float* out, float* stats, void* stream);
+int rai_chan_ln_bwd(const float* dout, const float* x, const float* bias, const float* gamma, const float* beta,
+                    const float* stats, int64_t rows, int32_t C, int32_t gelu, float* dx, float* dgamma,
+                    float* dbeta, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Conv / Linear bias + ReLU of the NatureCNN encoder (rl_algo_impls/shared/encoder/nature_cnn.py:10-53:
  * Conv2d -> ReLU x3, then Linear -> ReLU) over NHWC (or (B, C) row-major) rows, C % 4 == 0, C / 4
  * dividing 256.  Forward: out = relu(x + b[c]) (x = the bias-free conv / GEMM output).  Backward, one

@@ -31,6 +31,11 @@ RAI_SDE_MAX_H = 512
 RAI_SDE_MAX_A = 32
 RAI_MD_MAX_H = 512
 RAI_MD_MAX_G = 32
+RAI_CLN_MAX_C = 256
+# rai_chan_ln_bwd's row pass (csrc/chan_norm.hip): workgroup size, and the rows per row lane before another
+# workgroup is added (the tests size their multi-workgroup cases from these)
+CLN_THREADS = 256
+CLN_ROWS_PER_LANE = 8
 RAI_STAT_STRIDE = 5 + 2 * RAI_MAX_K
 ABI_VERSION = 1
 # the RAI_E_* return codes of include/rai_amd.h (tests/test_boundary.py checks them against the header)
@@ -206,6 +211,9 @@ _SIGNATURES = {
     "rai_se_residual_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rai_bias_gelu_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "rai_bias_gelu_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "rai_chan_ln_workspace_bytes": (_i64, [_i32]),
+    "rai_chan_ln_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, _vp, _vp, _vp]),
+    "rai_chan_ln_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "rai_gridnet_sample": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp,
                                      _vp]),
     "rai_gridnet_num_actions": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),

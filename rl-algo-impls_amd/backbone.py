@@ -11,7 +11,15 @@ Mirrors, for state_dict keys, parameter shapes and the seeded initialisation ord
 The backbone's convolutions run on MIOpen / hipBLASLt (the north star keeps the CNN contractions on
 PyTorch-ROCm).  The GridNet head's log-prob and entropy over every cell and sub-action is the fused
 HIP operator of gridnet.py (one launch forward, one backward) instead of the reference's H*W*7
-MaskedCategoricals.  Normalisation layers (`normalization=...`), the non-shared critic
+MaskedCategoricals.
+
+`normalization="layer"` (shared/module/normalization.py, channel_layer_norm.py) puts a
+ChannelLayerNorm2d after every backbone and critic convolution (unbiased variance over the channels
+of each pixel, eps 1e-5) and an nn.LayerNorm after the critic's Linear, at the reference's Sequential
+indices.  On NHWC fp32 GPU activations with C in {16, 32, 64, 128, 256} the convolution runs
+bias-free and bias + norm + GELU is one HIP pass forward and two launches backward
+(rai_chan_ln_fwd / _bwd, csrc/chan_norm.hip); elsewhere (CPU, NCHW, other widths) the modules' own
+torch path runs.  `normalization="batch"` / `"batch_renorm"`, the non-shared critic
 (`critic_shares_backbone=False`, `save_critic_separate`), the shared critic head and the Lux
 `pick_position` action space are outside the hot path and raise NotImplementedError.
 """
@@ -101,6 +109,118 @@ class _BiasGelu(torch.autograd.Function):
         return dx, db
 
 
+class ChannelLayerNorm2d(nn.Module):  # shared/module/channel_layer_norm.py
+    """gamma * (x - mean_c) / sqrt(var_c + eps) + beta over the channels of each pixel of an NCHW
+    tensor; var is torch's default unbiased one (C - 1), unlike nn.LayerNorm's.  This forward is the
+    CPU / NCHW / out-of-limits path; run_sequential fuses it with its convolution on the GPU."""
+
+    def __init__(self, num_channels: int, eps: float = 1e-5) -> None:
+        super().__init__()
+        self.eps = eps
+        self.gamma = nn.Parameter(torch.ones(1, num_channels, 1, 1))
+        self.beta = nn.Parameter(torch.zeros(1, num_channels, 1, 1))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        mean = x.mean(dim=1, keepdim=True)
+        var = x.var(dim=1, keepdim=True)
+        return self.gamma * (x - mean) / torch.sqrt(var + self.eps) + self.beta
+
+
+_NORMALIZATIONS = ("batch", "layer", "batch_renorm")  # shared/module/normalization.py:NormalizationMethod
+
+
+def _norm_method(method_name: str) -> str:
+    m = str(method_name).lower()
+    if m not in _NORMALIZATIONS:
+        raise KeyError(method_name)  # NormalizationMethod[method_name.upper()]
+    if m != "layer":
+        raise NotImplementedError(f"normalization '{m}' is not built (only 'layer' is): batch / batch_renorm "
+                                  "statistics across the captured rollout graph are outside the hot-path scope")
+    return m
+
+
+def normalization2d(method_name: str, num_features: int) -> nn.Module:
+    _norm_method(method_name)
+    return ChannelLayerNorm2d(num_features)
+
+
+def normalization1d(method_name: str, num_features: int) -> nn.Module:
+    _norm_method(method_name)
+    return nn.LayerNorm(num_features)
+
+
+class _ConvBiasChanLN(torch.autograd.Function):
+    """[GELU](ChannelLayerNorm2d(x + b)) over an NHWC bias-free conv output: one HIP pass forward
+    (rai_chan_ln_fwd) and the row pass + partial-sum launch backward (rai_chan_ln_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, b, gamma, beta, eps, gelu):
+        from . import _lib
+
+        C = int(x.shape[1])
+        rows = x.numel() // C
+        out = torch.empty_like(x)
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().rai_chan_ln_fwd(x.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rows, C,
+                                              float(eps), int(gelu), out.data_ptr(), stats.data_ptr(),
+                                              _lib.stream_handle(x.device)), "rai_chan_ln_fwd")
+        ctx.save_for_backward(x, b, gamma, beta, stats)
+        ctx.gelu = int(gelu)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import _lib
+
+        x, b, gamma, beta, stats = ctx.saved_tensors
+        C = int(x.shape[1])
+        rows = x.numel() // C
+        dout = dout.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty_like(x)
+        dpar = torch.empty((3, C), dtype=torch.float32, device=x.device)  # dgamma, dbeta, dbias
+        L = _lib.lib()
+        nb = int(L.rai_chan_ln_workspace_bytes(C))
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        _lib.check(L.rai_chan_ln_bwd(dout.data_ptr(), x.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                     stats.data_ptr(), rows, C, ctx.gelu, dx.data_ptr(), dpar[0].data_ptr(),
+                                     dpar[1].data_ptr(), dpar[2].data_ptr(), ws.data_ptr(), nb,
+                                     _lib.stream_handle(x.device)), "rai_chan_ln_bwd")
+        return dx, dpar[2], dpar[0].view(1, C, 1, 1), dpar[1].view(1, C, 1, 1), None, None
+
+
+def _conv_nobias(conv: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    if isinstance(conv, nn.ConvTranspose2d):
+        return torch.nn.functional.conv_transpose2d(x, conv.weight, None, conv.stride, conv.padding,
+                                                    conv.output_padding, conv.groups, conv.dilation)
+    return torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+
+
+def _chan_ln_fusable(C: int) -> bool:
+    from . import _lib
+
+    return 16 <= C <= _lib.RAI_CLN_MAX_C and C % 4 == 0 and (C // 4) & (C // 4 - 1) == 0
+
+
+def chan_ln_fused(y: torch.Tensor, bias: torch.Tensor, norm: ChannelLayerNorm2d, gelu: bool) -> torch.Tensor:
+    """The fused pass over a bias-free NHWC conv output (the one entry to the autograd Function)."""
+    return _ConvBiasChanLN.apply(y, bias, norm.gamma, norm.beta, norm.eps, gelu)
+
+
+def conv_norm(conv: nn.Module, norm: ChannelLayerNorm2d, x: torch.Tensor, gelu: bool) -> torch.Tensor:
+    """[GELU](norm(conv(x))) for a Conv2d / ConvTranspose2d with bias and a ChannelLayerNorm2d: on NHWC
+    fp32 GPU activations whose C the kernel takes (C / 4 a power of two, 16 <= C <= 256) the convolution
+    runs bias-free on MIOpen and bias + norm + GELU is one HIP pass; else the modules' own path."""
+    if (_nhwc(x) and conv.bias is not None and _chan_ln_fusable(int(conv.out_channels))
+            and norm.gamma.is_cuda and norm.gamma.dtype == torch.float32):
+        y = _conv_nobias(conv, x)
+        if _nhwc(y):
+            return chan_ln_fused(y, conv.bias, norm, gelu)
+        y = norm(y + conv.bias.view(1, -1, 1, 1))
+    else:
+        y = norm(conv(x))
+    return torch.nn.functional.gelu(y) if gelu else y
+
+
 def conv_gelu(conv: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """GELU(conv(x)) for a Conv2d / ConvTranspose2d with bias: on NHWC fp32 GPU activations the
     convolution runs bias-free on MIOpen and bias + GELU is one HIP pass; else the modules' own path."""
@@ -117,16 +237,25 @@ def conv_gelu(conv: nn.Module, x: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.gelu(conv(x))
 
 
+def _exact_gelu(m: nn.Module) -> bool:
+    return isinstance(m, nn.GELU) and m.approximate == "none"
+
+
 def run_sequential(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    """seq(x) with every (conv, GELU) pair through conv_gelu (same modules, same state_dict)."""
+    """seq(x) with every (conv, GELU) pair through conv_gelu and every (conv, ChannelLayerNorm2d[,
+    GELU]) run through conv_norm (same modules, same state_dict)."""
     mods = list(seq)
     i = 0
     while i < len(mods):
         m = mods[i]
-        if (isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)) and i + 1 < len(mods)
-                and isinstance(mods[i + 1], nn.GELU) and mods[i + 1].approximate == "none"):
+        is_conv = isinstance(m, (nn.Conv2d, nn.ConvTranspose2d))
+        if is_conv and i + 1 < len(mods) and _exact_gelu(mods[i + 1]):
             x = conv_gelu(m, x)
             i += 2
+        elif is_conv and i + 1 < len(mods) and isinstance(mods[i + 1], ChannelLayerNorm2d):
+            gelu = i + 2 < len(mods) and _exact_gelu(mods[i + 2])
+            x = conv_norm(m, mods[i + 1], x, gelu)
+            i += 3 if gelu else 2
         else:
             x = m(x)
             i += 1
@@ -169,20 +298,32 @@ class SqueezeExcitation(nn.Module):  # double_cone.py:18-47
         return x * self.fc(self.avg_pool(x).view(b, c)).view(b, c, 1, 1)
 
 
-class SEResidualBlock(nn.Module):  # double_cone.py:50-86 (normalization=None)
-    def __init__(self, channels: int, init_layers_orthogonal: bool = False) -> None:
+class SEResidualBlock(nn.Module):  # double_cone.py:50-86
+    """residual = conv, [norm], GELU, conv, [norm], SqueezeExcitation (the second norm has no GELU)."""
+
+    def __init__(self, channels: int, init_layers_orthogonal: bool = False,
+                 normalization: Optional[str] = None) -> None:
         super().__init__()
         conv = lambda: _init(nn.Conv2d(channels, channels, 3, padding=1), init_layers_orthogonal)
-        c0 = conv()
-        act = nn.GELU()
-        c1 = conv()
-        self.residual = nn.Sequential(c0, act, c1, SqueezeExcitation(channels,
-                                                                     init_layers_orthogonal=init_layers_orthogonal))
+        layers: List[nn.Module] = [conv()]
+        if normalization:
+            layers.append(normalization2d(normalization, channels))
+        layers.append(nn.GELU())
+        layers.append(conv())
+        if normalization:
+            layers.append(normalization2d(normalization, channels))
+        layers.append(SqueezeExcitation(channels, init_layers_orthogonal=init_layers_orthogonal))
+        self.residual = nn.Sequential(*layers)
         self.gelu = nn.GELU()
+        self._normalized = bool(normalization)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        conv0, act, conv1, se = self.residual
-        r = conv1(conv_gelu(conv0, x))  # act = GELU
+        if self._normalized:
+            conv0, norm0, act, conv1, norm1, se = self.residual
+            r = conv_norm(conv1, norm1, conv_norm(conv0, norm0, x, True), False)
+        else:
+            conv0, act, conv1, se = self.residual
+            r = conv1(conv_gelu(conv0, x))  # act = GELU
         b, c = r.shape[0], r.shape[1]
         s = se.fc(se.avg_pool(r).view(b, c))
         return se_residual_epilogue(x, r, s)  # == self.gelu(x + self.residual(x))
@@ -198,10 +339,13 @@ class SqueezeUnetBackbone(nn.Module):  # squeeze_unet.py:20-195
                  increment_kernel_size_on_down_conv: bool = False, normalization: Optional[str] = None) -> None:
         super().__init__()
         if normalization:
-            raise NotImplementedError("squeeze-U-Net normalization layers are outside the hot-path scope")
+            _norm_method(normalization)  # batch / batch_renorm: NotImplementedError
         orth = init_layers_orthogonal
         ch = list(channels_per_level)
-        se = lambda c, n: [SEResidualBlock(c, init_layers_orthogonal=orth) for _ in range(n)]
+        se = lambda c, n: [SEResidualBlock(c, init_layers_orthogonal=orth, normalization=normalization)
+                           for _ in range(n)]
+        # [conv, norm?, GELU]: the reference's Sequential indices with and without a normalization
+        post = lambda c: ([normalization2d(normalization, c)] if normalization else []) + [nn.GELU()]
 
         def down(cin: int, cout: int, stride) -> List[nn.Module]:
             mods: List[nn.Module] = []
@@ -209,18 +353,18 @@ class SqueezeUnetBackbone(nn.Module):  # squeeze_unet.py:20-195
                 k, pad = s, 0
                 if increment_kernel_size_on_down_conv and s % 2 == 0:  # squeeze_unet.py:47-55
                     k, pad = s + 1, 1
-                mods += [_init(nn.Conv2d(cin if i == 0 else cout, cout, kernel_size=k, stride=s, padding=pad), orth),
-                         nn.GELU()]
+                mods += [_init(nn.Conv2d(cin if i == 0 else cout, cout, kernel_size=k, stride=s, padding=pad), orth)]
+                mods += post(cout)
             return mods
 
         def up(cin: int, cout: int, stride) -> List[nn.Module]:
             mods: List[nn.Module] = []
             for i, s in enumerate(_as_list(stride)):
-                mods += [_init(nn.ConvTranspose2d(cin if i == 0 else cout, cout, kernel_size=s, stride=s), orth),
-                         nn.GELU()]
+                mods += [_init(nn.ConvTranspose2d(cin if i == 0 else cout, cout, kernel_size=s, stride=s), orth)]
+                mods += post(cout)
             return mods
 
-        head = [_init(nn.Conv2d(in_channels, ch[0], 3, padding=1), orth), nn.GELU()]
+        head = [_init(nn.Conv2d(in_channels, ch[0], 3, padding=1), orth)] + post(ch[0])
         self.encoders = nn.ModuleList([nn.Sequential(*(head + se(ch[0], encoder_residual_blocks_per_level[0])))])
         for lvl in range(1, len(ch)):
             self.encoders.append(nn.Sequential(*(down(ch[lvl - 1], ch[lvl], strides_per_level[lvl - 1])
@@ -315,12 +459,16 @@ class SqueezeUnetActorCriticNetwork(nn.Module):
             cin = ch[0]
             for s in flat_strides:
                 k = max(3, s)
-                mods += [_init(nn.Conv2d(cin, critic_channels, k, stride=s, padding=1 if k % 2 else 0), cnn_orth),
-                         nn.GELU()]
+                mods += [_init(nn.Conv2d(cin, critic_channels, k, stride=s, padding=1 if k % 2 else 0), cnn_orth)]
+                if normalization:
+                    mods.append(normalization2d(normalization, critic_channels))
+                mods.append(nn.GELU())
                 cin = critic_channels
             mods += [nn.AdaptiveAvgPool2d(1), nn.Flatten(),
-                     _init(nn.Linear(critic_channels, critic_channels), init_layers_orthogonal), nn.GELU(),
-                     _init(nn.Linear(critic_channels, 1), init_layers_orthogonal, std=1.0), act]
+                     _init(nn.Linear(critic_channels, critic_channels), init_layers_orthogonal)]
+            if normalization:  # (B, critic_channels): torch's LayerNorm
+                mods.append(normalization1d(normalization, critic_channels))
+            mods += [nn.GELU(), _init(nn.Linear(critic_channels, 1), init_layers_orthogonal, std=1.0), act]
             return nn.Sequential(*mods)
 
         acts = [_OUT_ACT[n]() for n in [output_activation_fn] + list(additional_critic_activation_functions or [])]

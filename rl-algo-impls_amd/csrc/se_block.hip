@@ -15,19 +15,13 @@
 // its ds partial in registers, and the 256 / C4 row-groups are summed in a fixed order through LDS
 // (deterministic).  Needs C % 4 == 0 and C / 4 dividing 256 (C in {4, 8, ..., 1024}).
 #include "common.h"
+#include "gelu.h"
 
 namespace {
 
 constexpr int SE_THREADS = 256;
 using f4 = float __attribute__((ext_vector_type(4)));
 typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gelu_f(float t) { return 0.5f * t * (1.f + erff(t * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad(float t) {
-  const float cdf = 0.5f * (1.f + erff(t * 0.70710678118654752f));
-  const float pdf = expf(-0.5f * t * t) * 0.39894228040143268f;
-  return cdf + t * pdf;
-}
 
 __global__ __launch_bounds__(SE_THREADS) void se_fwd_kernel(const f4* __restrict__ x, const f4* __restrict__ r,
                                                             const f4* __restrict__ s, int C4, int64_t HWC4,
