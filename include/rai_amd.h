@@ -106,6 +106,9 @@ int rai_gae_skips(const float* rewards, const float* values, const int32_t* step
  * logp_out / entropy_out (B,) fp32, either may be NULL (actions may be NULL when only
  * the entropy is wanted).  rai_gridnet_backward writes dL/dlogits for upstream
  * d_logp, d_entropy (B,).
+ * Every A up to RAI_GRID_MAX_A launches: the 64-cell tile takes 320 * A bytes of LDS, and
+ * where that passes a kernel's default 64 KiB (A >= 205; the sampler A >= 192) the entry
+ * point raises that kernel's dynamic-LDS limit once (81,920 B at A = 256).
  * ------------------------------------------------------------------------ */
 #define RAI_GRID_MAX_G 8
 #define RAI_GRID_MAX_A 256

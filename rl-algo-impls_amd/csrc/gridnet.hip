@@ -21,6 +21,7 @@
 // spread over the threads; the backward writes dz into the LDS tile in place and stores the span
 // coalesced.  Sums over a sample's items are fixed-order block reductions (deterministic).
 #include <algorithm>
+#include <mutex>
 
 #include "common.h"
 
@@ -324,7 +325,33 @@ int setup(GridArgs& a, const float* logits, const uint8_t* mask, const int64_t* 
   return RAI_OK;
 }
 
+// Dynamic LDS of the three tile kernels: the 64-cell tile's logits and mask bytes, 320 B per logit column whatever
+// C is.  A = 78 (MicroRTS) asks for 24,960 B; A = RAI_GRID_MAX_A for 81,920 B, beside 64 B (forward / backward) or
+// 4,128 B (sampler) of static LDS.  That passes a kernel's default 64 KiB limit from A = 205 (sampler: A = 192), so
+// allow_tile() raises the limit before such a launch; a CU's 160 KB hold the largest tile with room to spare.
 size_t smem_bytes(int A) { return (size_t)GN_CELLS * A * (sizeof(float) + 1); }
+
+constexpr size_t GN_LDS_PLAIN = 56 * 1024;  // requests up to here fit the default limit beside either kernel's static LDS
+static_assert(GN_LDS_PLAIN + 2 * GN_CELLS * RAI_GRID_MAX_G * 4 + 64 <= 64 * 1024, "static LDS of the sampler");
+static_assert((size_t)GN_CELLS * RAI_GRID_MAX_A * 5 + 2 * GN_CELLS * RAI_GRID_MAX_G * 4 + 64 <= 160 * 1024,
+              "the largest tile fits a CU's LDS");
+
+// Raise a kernel's dynamic-LDS limit to its largest tile, once per kernel (a host call, as conv.hip's allow_lds);
+// launches whose tile fits the default limit (every A <= 179, MicroRTS's 78 among them) do not come here.
+int allow_tile(const void* kernel, size_t bytes) {
+  if (bytes <= GN_LDS_PLAIN) return RAI_OK;
+  static std::mutex mu;
+  static const void* done[3];
+  static int ndone = 0;
+  std::lock_guard<std::mutex> lock(mu);
+  for (int i = 0; i < ndone; ++i)
+    if (done[i] == kernel) return RAI_OK;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)smem_bytes(RAI_GRID_MAX_A));
+  if (e != hipSuccess) return (int)e;
+  if (ndone < 3) done[ndone++] = kernel;
+  return RAI_OK;
+}
 
 }  // namespace
 
@@ -339,6 +366,8 @@ extern "C" int rai_gridnet_logp_entropy(const float* logits, const uint8_t* mask
   if (B == 0) return RAI_OK;
   a.logp = logp_out;
   a.ent = entropy_out;
+  rc = allow_tile(reinterpret_cast<const void*>(&gridnet_kernel<false>), smem_bytes(a.A));
+  if (rc != RAI_OK) return rc;
   hipLaunchKernelGGL(gridnet_kernel<false>, dim3((unsigned)B), dim3(GN_THREADS), smem_bytes(a.A),
                      rai_stream(stream), a);
   RAI_LAUNCH_CHECK();
@@ -357,6 +386,8 @@ extern "C" int rai_gridnet_backward(const float* logits, const uint8_t* mask, co
   a.d_logp = d_logp;
   a.d_ent = d_entropy;
   a.d_logits = d_logits;
+  rc = allow_tile(reinterpret_cast<const void*>(&gridnet_kernel<true>), smem_bytes(a.A));
+  if (rc != RAI_OK) return rc;
   hipLaunchKernelGGL(gridnet_kernel<true>, dim3((unsigned)B), dim3(GN_THREADS), smem_bytes(a.A),
                      rai_stream(stream), a);
   RAI_LAUNCH_CHECK();
@@ -376,6 +407,8 @@ extern "C" int rai_gridnet_sample(const float* logits, const uint8_t* mask, int6
   a.logp = logp_out;
   a.seed = seed;
   a.offset = offset;
+  rc = allow_tile(reinterpret_cast<const void*>(&gridnet_sample_kernel), smem_bytes(a.A));
+  if (rc != RAI_OK) return rc;
   hipLaunchKernelGGL(gridnet_sample_kernel, dim3((unsigned)B), dim3(GN_THREADS), smem_bytes(a.A),
                      rai_stream(stream), a);
   RAI_LAUNCH_CHECK();
