@@ -841,18 +841,23 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       RELANE();
       f4 gr[MC_CPT];
       const int gbase = (int)M8_S2_OFF + (net * 2 + par) * WL_N * (int)sizeof(float);
+      // the 2G share norms (net-major, CU order), lane l polling the granules of number l until both
+      // carry this step's tag (they were stored before their CU's round-2 arrival); fixed-order wave sum.
+      // The granule loads are issued AHEAD of the gradient's five: loads return in order, so the first poll
+      // waits for the granules alone (vmcnt(5)) and the norm chain below (fp64 wave sum, sqrt, the clip
+      // coefficient's divide) runs while the 19 KB of gradient are in flight.  A failed first poll (rare)
+      // polls again behind the gradient loads and then waits for them too.
+      static_assert(MC_NW == 4, "four wave parts per share norm");
+      const unsigned long long* gq = sq_gran + (par * 2 * G + min(lane, 2 * G - 1)) * 2;
+      const unsigned tag = (unsigned)(step0 + mb + 1);
+      unsigned long long qh = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unsigned long long ql = __hip_atomic_load(gq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
       for (int i = 0; i < MC_CPT; ++i) {
         const int chl = min(tid + MC_NT * i, WL_CH - 1);
         gr[i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srs, gbase + 16 * chl, 0, 16));
       }
-      // the 2G share norms (net-major, CU order), lane l polling the granules of number l until both
-      // carry this step's tag (they were stored before their CU's round-2 arrival); fixed-order wave sum
-      static_assert(MC_NW == 4, "four wave parts per share norm");
-      const unsigned long long* gq = sq_gran + (par * 2 * G + min(lane, 2 * G - 1)) * 2;
-      const unsigned tag = (unsigned)(step0 + mb + 1);
-      unsigned long long qh, ql;
-      {
+      if (!__all((unsigned)(qh >> 32) == tag && (unsigned)(ql >> 32) == tag)) {
         const unsigned long long t0 = rai_clock();
         for (;;) {
           qh = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -872,8 +877,12 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
       const float total_norm = (float)sqrt(tot);
       STAMP(14);
       const float coef = clip_coef(max_grad_norm, total_norm);
-      // branch-free over the chunks (one basic block: the transcendentals of all chunks interleave); a lane
-      // past the last chunk updates a clamped copy and stores nothing (its moments are never written back)
+      STAMP(20);
+      // One basic block over the chunks every thread owns (all but the last: their S.Wt store carries no lane
+      // test, so nothing of their update is sunk into a per-chunk branch): chunk i starts when its own load
+      // has landed (vmcnt(4 - i)) and one chunk's packed ops fill another's sqrt / rcp latency.  In the last
+      // chunk a lane past WL_CH updates a clamped copy and stores nothing (its moments are never written back).
+      static_assert(MC_NT * (MC_CPT - 1) <= WL_CH, "only the last chunk has lanes past the end");
 #pragma unroll
       for (int i = 0; i < MC_CPT; ++i) {
         const int ch = tid + MC_NT * i;
@@ -893,11 +902,12 @@ __device__ __forceinline__ void mlp_mc8(const MlpArgs& a, SmemM8<OUTP, G, RCV>& 
             vreg[i][2 * h] = vv.x;
             vreg[i][2 * h + 1] = vv.y;
           }
-          if (ch < WL_CH) *reinterpret_cast<f4*>(&S.Wt[4 * ch]) = p;
+          if (i + 1 < MC_CPT || ch < WL_CH) *reinterpret_cast<f4*>(&S.Wt[4 * ch]) = p;
         }
       }
       if (ACTOR && c == 0 && tid == 0 && a.norms && norm0 + mb < a.max_norms) a.norms[norm0 + mb] = total_norm;
     }
+    STAMP(21);  // work done; the barrier wait follows
     lds_barrier();
     STAMP(8);
   }

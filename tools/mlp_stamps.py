@@ -57,7 +57,7 @@ print(f"epoch {ev0.elapsed_time(ev1):.2f} ms for {nmb} minibatches -> {ev0.elaps
 # mc8: STAMP(15..19) close each compute phase's work and STAMP(1..5) the barrier wait after it; the exchange
 # phases are split by STAMP(9..14).  Every stamp is the time since the previous one, so a phase's time is
 # the sum of its work and wait stamps and the % column is over all of them (work plus waits).
-MC8_PARTS = [(15, 1), (16, 2), (17, 3), (18, 4), (19, 5), (9, 10, 6), (11, 12, 13, 7), (14, 8)]
+MC8_PARTS = [(15, 1), (16, 2), (17, 3), (18, 4), (19, 5), (9, 10, 6), (11, 12, 13, 7), (14, 20, 21, 8)]
 if LAYOUT == "mc8":  # slot 31: launches whose network ran on one XCC (plain-store hand-offs)
     print(f"one-XCC store form: actor {st[0, 31]:.0f}, critic {st[1, 31]:.0f} of 1 launch")
 for net in range(2):
@@ -76,5 +76,6 @@ for net in range(2):
                      (6, "  r1: counter wait + stats"), (11, "  r2: share-sum loads (+ xGMI)"),
                      (12, "  r2: share store + norm + drain"), (13, "  r2: barrier (other waves' drains)"),
                      (7, "  r2: counter wait (both networks)"), (14, "  ag: gradient + norm loads, norm sum"),
-                     (8, "  ag: clip + adam + barrier")):
+                     (20, "  ag: clip coefficient"), (21, "  ag: adam over the 5 chunks"),
+                     (8, "  ag: barrier wait")):
             print(f"  {n:34s} {st[net, i] / nmb:10.1f} ticks/mb")
