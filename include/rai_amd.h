@@ -189,6 +189,37 @@ int rai_chan_ln_bwd(const float* dout, const float* x, const float* bias, const 
                     const float* stats, int64_t rows, int32_t C, int32_t gelu, float* dx, float* dgamma,
                     float* dbeta, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Squeeze-excitation gate of the DoubleCone backbone's SE blocks (SqueezeExcitation.forward,
+ * rl_algo_impls/shared/policy/actor_critic_network/double_cone.py:43-47):
+ * s = sigmoid(W2 . GELU(W1 . mean_hw r)).  r, dr: NHWC fp32 (B, HW, C), C fastest; W1 (M, C) and W2 (C, M)
+ * bias-free, row-major, 4-byte aligned only (views into the flat parameter buffer); s, ds, pooled (B, C);
+ * hidden (B, M).  GELU is the exact erf form.
+ *   forward (one launch):  pooled = sum_hw r / HW;  hidden = W1 pooled;  s = sigmoid(W2 GELU(hidden)).
+ *   backward (two launches):  dz2 = ds s (1 - s);  da = W2^T dz2;  dh = da GELU'(hidden);  dpool = W1^T dh;
+ *     dr[b, p, :] += dpool / HW  IN PLACE (dr holds rai_se_residual_bwd's dr on entry);
+ *     dw2 = sum_b dz2 (x) GELU(hidden),  dw1 = sum_b dh (x) pooled  (written, not accumulated).
+ *     A workgroup owns a fixed run of samples, ceil(B / RAI_SEG_MAX_BLOCKS), in chunks of RAI_SEG_CHUNK;
+ *     its weight-gradient terms go to its workspace slot and the second launch sums the slots
+ *     RAI_SEG_FIN_LANES side by side, in a fixed order: no float atomics, no counters, nothing to zero,
+ *     and two calls on the same inputs give the same bits.
+ * C % 16 == 0, C / 4 dividing 256, M == C / 16 <= 64, HW >= 1, else RAI_E_SHAPE.  B == 0: RAI_OK, and the
+ * backward zeroes dw1, dw2.  r, dr, pooled and workspace must be 16-byte aligned, workspace at least
+ * rai_se_gate_workspace_bytes(C) bytes (RAI_E_WORKSPACE otherwise); one workspace per concurrently
+ * running launch. */
+#define RAI_SEG_CHUNK 4
+#define RAI_SEG_MAX_BLOCKS 256
+#define RAI_SEG_FIN_LANES 16
+int64_t rai_se_gate_workspace_bytes(int32_t C);
+int rai_se_gate_fwd(const float* r, const float* w1, const float* w2, int64_t B, int32_t C, int32_t HW, int32_t M,
+                    float* s, float* pooled, float* hidden, void* stream);
+int rai_se_gate_bwd(const float* ds, const float* s, const float* pooled, const float* hidden, const float* w1,
+                    const float* w2, int64_t B, int32_t C, int32_t HW, int32_t M, float* dr, float* dw1, float* dw2,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+/* The DoubleCone block's last up-convolution (double_cone.py:130-131): out = skip + GELU(x + b[c]) over
+ * NHWC rows, C % 4 == 0; x, skip, out 16-byte aligned.  Backward: dskip = dout, dx = rai_bias_gelu_bwd. */
+int rai_bias_gelu_add_fwd(const float* x, const float* b, const float* skip, int64_t rows, int32_t C, float* out,
+                          void* stream);
+
 /* Conv / Linear bias + ReLU of the NatureCNN encoder (rl_algo_impls/shared/encoder/nature_cnn.py:10-53:
  * Conv2d -> ReLU x3, then Linear -> ReLU) over NHWC (or (B, C) row-major) rows, C % 4 == 0, C / 4
  * dividing 256.  Forward: out = relu(x + b[c]) (x = the bias-free conv / GEMM output).  Backward, one

@@ -36,6 +36,11 @@ RAI_CLN_MAX_C = 256
 # workgroup is added (the tests size their multi-workgroup cases from these)
 CLN_THREADS = 256
 CLN_ROWS_PER_LANE = 8
+# rai_se_gate_bwd (csrc/se_gate.hip): samples per chunk, workgroups (= workspace slots) at most, and the
+# slots the finalize sums side by side
+RAI_SEG_CHUNK = 4
+RAI_SEG_MAX_BLOCKS = 256
+RAI_SEG_FIN_LANES = 16
 RAI_STAT_STRIDE = 5 + 2 * RAI_MAX_K
 ABI_VERSION = 1
 # the RAI_E_* return codes of include/rai_amd.h (tests/test_boundary.py checks them against the header)
@@ -211,6 +216,11 @@ _SIGNATURES = {
     "rai_se_residual_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rai_bias_gelu_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "rai_bias_gelu_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "rai_se_gate_workspace_bytes": (_i64, [_i32]),
+    "rai_se_gate_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rai_se_gate_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64,
+                                  _vp]),
+    "rai_bias_gelu_add_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "rai_chan_ln_workspace_bytes": (_i64, [_i32]),
     "rai_chan_ln_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "rai_chan_ln_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -22,6 +22,18 @@ bias-free and bias + norm + GELU is one HIP pass forward and two launches backwa
 torch path runs.  `normalization="batch"` / `"batch_renorm"`, the non-shared critic
 (`critic_shares_backbone=False`, `save_critic_separate`), the shared critic head and the Lux
 `pick_position` action space are outside the hot path and raise NotImplementedError.
+
+DoubleCone (actor_head_style: double_cone; double_cone.py:89-228): DoubleConeBlock (a 4x4 stride-4
+convolution down to the cone's map, the cone's SE blocks, two 2x2 transposed convolutions up, and the
+skip add), DoubleConeBackbone (in_block, double_cone, out_block) and DoubleConeActorCritic under the same
+BackboneActorCritic heads as the squeeze-U-Net, which is now a subclass of it with unchanged keys and
+construction order.  The network's SE blocks compute their gate s = sigmoid(W2 . GELU(W1 . mean_hw r))
+in ONE launch (rai_se_gate_fwd, csrc/se_gate.hip) and its backward in two, adding into the epilogue's dr
+in place (_SETail: two launches forward, three backward, instead of the torch gate's ~5 and ~10);
+C % 16 == 0, C / 4 dividing 256, C <= 1024, NHWC fp32 on the GPU, else the torch gate.  SEResidualBlock's
+`fused_gate` attribute is off by default: the squeeze-U-Net's blocks keep their path.  RAI_SE_GATE=0 keeps
+the torch gate in DoubleCone too.  The cone's last up-convolution adds its skip inside the bias + GELU pass
+(rai_bias_gelu_add_fwd).  DoubleCone takes no normalization (the reference passes none on).
 """
 from __future__ import annotations
 
@@ -107,6 +119,82 @@ class _BiasGelu(torch.autograd.Function):
         # NHWC: dx viewed (rows, C) is contiguous; the bias gradient is its column sum
         db = dx.permute(0, 2, 3, 1).reshape(-1, C).sum(0)
         return dx, db
+
+
+class _BiasGeluAdd(torch.autograd.Function):
+    """skip + GELU(x + b) over an NHWC conv output (rai_bias_gelu_add_fwd): the DoubleCone block's last
+    up-convolution and its skip add in one pass.  Backward: dskip = dout, dx by rai_bias_gelu_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, b, skip):
+        from . import _lib
+
+        C = int(x.shape[1])
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().rai_bias_gelu_add_fwd(x.data_ptr(), b.data_ptr(), skip.data_ptr(), x.numel() // C, C,
+                                                    out.data_ptr(), _lib.stream_handle(x.device)),
+                   "rai_bias_gelu_add_fwd")
+        ctx.save_for_backward(x, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, db = _BiasGelu.backward(ctx, dy)
+        return dx, db, dy
+
+
+# The fused squeeze-excitation gate (csrc/se_gate.hip) of the DoubleCone blocks; RAI_SE_GATE=0 keeps the
+# torch gate (AdaptiveAvgPool2d, two Linears, GELU, sigmoid) for A/B runs.
+_SE_GATE = os.environ.get("RAI_SE_GATE", "1") == "1"
+
+
+def _se_gate_fusable(C: int) -> bool:
+    return C >= 16 and C % 16 == 0 and 256 % (C // 4) == 0 and C // 16 <= 64
+
+
+class _SETail(torch.autograd.Function):
+    """GELU(x + r * s(r)), s = sigmoid(W2 . GELU(W1 . mean_hw r)) (double_cone.py:43-47,85-86), from
+    (x, r, W1, W2): rai_se_gate_fwd then rai_se_residual_fwd forward (two launches); rai_se_residual_bwd,
+    then rai_se_gate_bwd adding the gate's term into that dr in place, backward (three launches)."""
+
+    @staticmethod
+    def forward(ctx, x, r, w1, w2):
+        from . import _lib
+
+        B, C, H, W = (int(d) for d in x.shape)
+        M = int(w1.shape[0])
+        w1, w2 = w1.contiguous(), w2.contiguous()
+        s = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        pooled = torch.empty_like(s)
+        hidden = torch.empty((B, M), dtype=torch.float32, device=x.device)
+        out = torch.empty_like(x)
+        L, st = _lib.lib(), _lib.stream_handle(x.device)
+        _lib.check(L.rai_se_gate_fwd(r.data_ptr(), w1.data_ptr(), w2.data_ptr(), B, C, H * W, M, s.data_ptr(),
+                                     pooled.data_ptr(), hidden.data_ptr(), st), "rai_se_gate_fwd")
+        _lib.check(L.rai_se_residual_fwd(x.data_ptr(), r.data_ptr(), s.data_ptr(), B, C, H * W, out.data_ptr(), st),
+                   "rai_se_residual_fwd")
+        ctx.save_for_backward(x, r, w1, w2, s, pooled, hidden)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import _lib
+
+        x, r, w1, w2, s, pooled, hidden = ctx.saved_tensors
+        B, C, H, W = (int(d) for d in x.shape)
+        M = int(w1.shape[0])
+        dout = dout.contiguous(memory_format=torch.channels_last)
+        dx, dr, ds = torch.empty_like(x), torch.empty_like(r), torch.empty_like(s)
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        L, st = _lib.lib(), _lib.stream_handle(x.device)
+        _lib.check(L.rai_se_residual_bwd(dout.data_ptr(), x.data_ptr(), r.data_ptr(), s.data_ptr(), B, C, H * W,
+                                         dx.data_ptr(), dr.data_ptr(), ds.data_ptr(), st), "rai_se_residual_bwd")
+        nb = int(L.rai_se_gate_workspace_bytes(C))
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        _lib.check(L.rai_se_gate_bwd(ds.data_ptr(), s.data_ptr(), pooled.data_ptr(), hidden.data_ptr(), w1.data_ptr(),
+                                     w2.data_ptr(), B, C, H * W, M, dr.data_ptr(), dw1.data_ptr(), dw2.data_ptr(),
+                                     ws.data_ptr(), nb, st), "rai_se_gate_bwd")
+        return dx, dr, dw1, dw2
 
 
 class ChannelLayerNorm2d(nn.Module):  # shared/module/channel_layer_norm.py
@@ -316,6 +404,8 @@ class SEResidualBlock(nn.Module):  # double_cone.py:50-86
         self.residual = nn.Sequential(*layers)
         self.gelu = nn.GELU()
         self._normalized = bool(normalization)
+        # the gate as one HIP launch (_SETail); off here, DoubleConeBackbone turns it on for its blocks
+        self.fused_gate = False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._normalized:
@@ -325,6 +415,10 @@ class SEResidualBlock(nn.Module):  # double_cone.py:50-86
             conv0, act, conv1, se = self.residual
             r = conv1(conv_gelu(conv0, x))  # act = GELU
         b, c = r.shape[0], r.shape[1]
+        w1, w2 = se.fc[0].weight, se.fc[2].weight
+        if (self.fused_gate and _nhwc(x) and _nhwc(r) and r.shape == x.shape and _se_gate_fusable(int(c))
+                and w1.is_cuda and w1.dtype == torch.float32):
+            return _SETail.apply(x, r, w1, w2)
         s = se.fc(se.avg_pool(r).view(b, c))
         return se_residual_epilogue(x, r, s)  # == self.gelu(x + self.residual(x))
 
@@ -407,37 +501,32 @@ class _HStack(nn.ModuleList):  # shared/module/stack.py
 _OUT_ACT = {"tanh": nn.Tanh, "relu": nn.ReLU, "identity": nn.Identity, "sigmoid": nn.Sigmoid}
 
 
-class SqueezeUnetActorCriticNetwork(nn.Module):
-    """squeeze_unet.py:198-270 + backbone_actor_critic.py:31-232 (per-position GridNet actions)."""
+def _check_shared_critic(critic_shares_backbone: bool, save_critic_separate: bool, shared_critic_head: bool) -> None:
+    if not critic_shares_backbone or save_critic_separate or shared_critic_head:
+        raise NotImplementedError("non-shared / shared-head critics are outside the hot-path scope")
 
-    def __init__(self, observation_space, action_space, action_plane_space, init_layers_orthogonal: bool = True,
-                 cnn_layers_init_orthogonal: Optional[bool] = None, channels_per_level: Optional[List[int]] = None,
-                 strides_per_level: Optional[Strides] = None, deconv_strides_per_level: Optional[Strides] = None,
-                 encoder_residual_blocks_per_level: Optional[List[int]] = None,
-                 decoder_residual_blocks_per_level: Optional[List[int]] = None, num_additional_critics: int = 0,
+
+class BackboneActorCritic(nn.Module):
+    """backbone_actor_critic.py:31-252 (per-position GridNet actions): the actor head and the critic
+    heads over a built backbone's (B, backbone_out_channels, H, W) features.  `strides`: the critic
+    heads' down-convolutions."""
+
+    def __init__(self, observation_space, action_space, action_plane_space, backbone: nn.Module,
+                 backbone_out_channels: int, num_additional_critics: int = 0,
                  additional_critic_activation_functions: Optional[List[str]] = None, critic_channels: int = 64,
-                 increment_kernel_size_on_down_conv: bool = False, output_activation_fn: str = "identity",
+                 init_layers_orthogonal: bool = True, cnn_layers_init_orthogonal: bool = False,
+                 strides: Strides = (2, 2), output_activation_fn: str = "identity",
                  subaction_mask: Optional[Dict[int, Dict[int, int]]] = None, critic_shares_backbone: bool = True,
                  save_critic_separate: bool = False, shared_critic_head: bool = False,
                  normalization: Optional[str] = None) -> None:
         super().__init__()
-        if not critic_shares_backbone or save_critic_separate or shared_critic_head:
-            raise NotImplementedError("non-shared / shared-head critics are outside the hot-path scope")
-        cnn_orth = bool(cnn_layers_init_orthogonal) if cnn_layers_init_orthogonal is not None else False
-        ch = list(channels_per_level or [64, 128, 256])
-        strides = list(strides_per_level or [2] * (len(ch) - 1))
-        enc_blocks = list(encoder_residual_blocks_per_level or [1] * len(ch))
-        dec_blocks = list(decoder_residual_blocks_per_level or enc_blocks[:-1])
-        assert len(strides) == len(ch) - 1 and len(enc_blocks) == len(ch) and len(dec_blocks) == len(ch) - 1
+        _check_shared_critic(critic_shares_backbone, save_critic_separate, shared_critic_head)
+        cnn_orth = bool(cnn_layers_init_orthogonal)
         if num_additional_critics and not additional_critic_activation_functions:
             additional_critic_activation_functions = ["identity"] * num_additional_critics
         # construction order = the reference's (backbone, actor head, critic heads): the seeded
         # default initialisation consumes the RNG identically
-        self.backbone = SqueezeUnetBackbone(int(observation_space.shape[0]), ch, strides, enc_blocks, dec_blocks,
-                                            deconv_strides_per_level=deconv_strides_per_level,
-                                            init_layers_orthogonal=cnn_orth,
-                                            increment_kernel_size_on_down_conv=increment_kernel_size_on_down_conv,
-                                            normalization=normalization)
+        self.backbone = backbone
         self.range_size = float(np.max(observation_space.high) - np.min(observation_space.low))
         self.action_vec = np.asarray(action_plane_space.nvec)
         if isinstance(action_space, dict) or hasattr(action_space, "spaces"):
@@ -447,8 +536,8 @@ class SqueezeUnetActorCriticNetwork(nn.Module):
         self._sub = (ValueDependentMask.from_reference_index_to_index_to_value(subaction_mask)
                      if subaction_mask else None)
         self.actor_head = nn.Sequential(
-            _init(nn.Conv2d(ch[0], int(self.action_vec.sum()), kernel_size=3, padding=1), init_layers_orthogonal,
-                  std=0.01),
+            _init(nn.Conv2d(backbone_out_channels, int(self.action_vec.sum()), kernel_size=3, padding=1),
+                  init_layers_orthogonal, std=0.01),
             _Transpose((0, 2, 3, 1)))
         flat_strides: List[int] = []
         for s in strides:
@@ -456,7 +545,7 @@ class SqueezeUnetActorCriticNetwork(nn.Module):
 
         def critic(act: nn.Module) -> nn.Sequential:  # backbone_actor_critic.py:111-171
             mods: List[nn.Module] = []
-            cin = ch[0]
+            cin = backbone_out_channels
             for s in flat_strides:
                 k = max(3, s)
                 mods += [_init(nn.Conv2d(cin, critic_channels, k, stride=s, padding=1 if k % 2 else 0), cnn_orth)]
@@ -490,7 +579,7 @@ class SqueezeUnetActorCriticNetwork(nn.Module):
 
     def distribution_and_value(self, obs: torch.Tensor, action_masks: torch.Tensor):
         if action_masks is None:
-            raise AssertionError("No mask case unhandled in SqueezeUnetActorCriticNetwork")
+            raise AssertionError(f"No mask case unhandled in {self.__class__.__name__}")
         o = self._preprocess(obs)
         x = self.backbone(o)
         pi = GridnetDistribution(int(np.prod(o.shape[-2:])), self.action_vec, self.actor_head(x), action_masks,
@@ -521,3 +610,117 @@ class SqueezeUnetActorCriticNetwork(nn.Module):
     @property
     def value_shape(self):
         return (self._critic_features,) if self._critic_features > 1 else ()
+
+
+class SqueezeUnetActorCriticNetwork(BackboneActorCritic):
+    """squeeze_unet.py:198-270: the squeeze-U-Net backbone under BackboneActorCritic's heads."""
+
+    def __init__(self, observation_space, action_space, action_plane_space, init_layers_orthogonal: bool = True,
+                 cnn_layers_init_orthogonal: Optional[bool] = None, channels_per_level: Optional[List[int]] = None,
+                 strides_per_level: Optional[Strides] = None, deconv_strides_per_level: Optional[Strides] = None,
+                 encoder_residual_blocks_per_level: Optional[List[int]] = None,
+                 decoder_residual_blocks_per_level: Optional[List[int]] = None, num_additional_critics: int = 0,
+                 additional_critic_activation_functions: Optional[List[str]] = None, critic_channels: int = 64,
+                 increment_kernel_size_on_down_conv: bool = False, output_activation_fn: str = "identity",
+                 subaction_mask: Optional[Dict[int, Dict[int, int]]] = None, critic_shares_backbone: bool = True,
+                 save_critic_separate: bool = False, shared_critic_head: bool = False,
+                 normalization: Optional[str] = None) -> None:
+        _check_shared_critic(critic_shares_backbone, save_critic_separate, shared_critic_head)
+        cnn_orth = bool(cnn_layers_init_orthogonal) if cnn_layers_init_orthogonal is not None else False
+        ch = list(channels_per_level or [64, 128, 256])
+        strides = list(strides_per_level or [2] * (len(ch) - 1))
+        enc_blocks = list(encoder_residual_blocks_per_level or [1] * len(ch))
+        dec_blocks = list(decoder_residual_blocks_per_level or enc_blocks[:-1])
+        assert len(strides) == len(ch) - 1 and len(enc_blocks) == len(ch) and len(dec_blocks) == len(ch) - 1
+        backbone = SqueezeUnetBackbone(int(observation_space.shape[0]), ch, strides, enc_blocks, dec_blocks,
+                                       deconv_strides_per_level=deconv_strides_per_level,
+                                       init_layers_orthogonal=cnn_orth,
+                                       increment_kernel_size_on_down_conv=increment_kernel_size_on_down_conv,
+                                       normalization=normalization)
+        super().__init__(observation_space, action_space, action_plane_space, backbone, ch[0],
+                         num_additional_critics=num_additional_critics,
+                         additional_critic_activation_functions=additional_critic_activation_functions,
+                         critic_channels=critic_channels, init_layers_orthogonal=init_layers_orthogonal,
+                         cnn_layers_init_orthogonal=cnn_orth, strides=strides,
+                         output_activation_fn=output_activation_fn, subaction_mask=subaction_mask,
+                         normalization=normalization)
+
+
+class DoubleConeBlock(nn.Module):  # double_cone.py:89-131
+    """x + up_conv(res_blocks(gelu(pool_conv(x)))): a 4x4 stride-4 convolution down to the cone's map,
+    the cone's SE blocks there, and two 2x2 stride-2 transposed convolutions back up."""
+
+    def __init__(self, channels: int, pooled_channels: int, num_residual_blocks: int = 6,
+                 init_layers_orthogonal: bool = False, gelu_pool_conv: bool = True) -> None:
+        super().__init__()
+        orth = init_layers_orthogonal
+        self.pool_conv = _init(nn.Conv2d(channels, pooled_channels, 4, stride=4), orth)
+        self.gelu = nn.GELU() if gelu_pool_conv else nn.Identity()
+        self.res_blocks = nn.Sequential(*[SEResidualBlock(pooled_channels, init_layers_orthogonal=orth)
+                                          for _ in range(num_residual_blocks)])
+        mid = (channels + pooled_channels) // 2
+        self.up_conv = nn.Sequential(_init(nn.ConvTranspose2d(pooled_channels, mid, 2, stride=2), orth), nn.GELU(),
+                                     _init(nn.ConvTranspose2d(mid, channels, 2, stride=2), orth), nn.GELU())
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        assert x.shape[-2] % 4 == 0 and x.shape[-1] % 4 == 0, (
+            f"DoubleConeBlock needs a map whose height and width are multiples of 4, got {tuple(x.shape[-2:])}")
+        # (gelu_pool_conv=False: the plain convolution with its bias)
+        p = conv_gelu(self.pool_conv, x) if _exact_gelu(self.gelu) else self.gelu(self.pool_conv(x))
+        p = run_sequential(self.res_blocks, p)
+        up0, _, up1, _ = self.up_conv
+        u = conv_gelu(up0, p)
+        if _nhwc(u) and _nhwc(x) and up1.out_channels % 4 == 0:
+            y = _conv_nobias(up1, u)
+            if _nhwc(y) and y.shape == x.shape:
+                return _BiasGeluAdd.apply(y, up1.bias, x)  # x + GELU(y + bias) in one pass
+            return x + torch.nn.functional.gelu(y + up1.bias.view(1, -1, 1, 1))
+        return x + conv_gelu(up1, u)
+
+
+class DoubleConeBackbone(nn.Module):  # double_cone.py:134-179
+    def __init__(self, in_channels: int, channels: int, pooled_channels: int, init_layers_orthogonal: bool = False,
+                 in_num_res_blocks: int = 4, cone_num_res_blocks: int = 6, out_num_res_blocks: int = 4,
+                 gelu_pool_conv: bool = True) -> None:
+        super().__init__()
+        orth = init_layers_orthogonal
+        se = lambda n: [SEResidualBlock(channels, init_layers_orthogonal=orth) for _ in range(n)]
+        self.in_block = nn.Sequential(_init(nn.Conv2d(in_channels, channels, 3, padding=1), orth), nn.GELU(),
+                                      *se(in_num_res_blocks))
+        self.double_cone = DoubleConeBlock(channels, pooled_channels, num_residual_blocks=cone_num_res_blocks,
+                                           init_layers_orthogonal=orth, gelu_pool_conv=gelu_pool_conv)
+        self.out_block = nn.Sequential(*se(out_num_res_blocks))
+        set_fused_gate(self, _SE_GATE)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return run_sequential(self.out_block, self.double_cone(run_sequential(self.in_block, x)))
+
+
+def set_fused_gate(module: nn.Module, on: bool) -> None:
+    """Turn the one-launch SE gate (rai_se_gate_fwd / _bwd) on or off for every SE block under `module`."""
+    for m in module.modules():
+        if isinstance(m, SEResidualBlock):
+            m.fused_gate = bool(on)
+
+
+class DoubleConeActorCritic(BackboneActorCritic):
+    """double_cone.py:182-228.  The reference passes no normalization on to this network."""
+
+    def __init__(self, observation_space, action_space, action_plane_space, init_layers_orthogonal: bool = True,
+                 cnn_layers_init_orthogonal: Optional[bool] = None, backbone_channels: int = 128,
+                 pooled_channels: int = 512, critic_channels: int = 64, in_num_res_blocks: int = 4,
+                 cone_num_res_blocks: int = 6, out_num_res_blocks: int = 4, num_additional_critics: int = 0,
+                 additional_critic_activation_functions: Optional[List[str]] = None, gelu_pool_conv: bool = True,
+                 output_activation_fn: str = "identity",
+                 subaction_mask: Optional[Dict[int, Dict[int, int]]] = None) -> None:
+        cnn_orth = bool(cnn_layers_init_orthogonal) if cnn_layers_init_orthogonal is not None else False
+        backbone = DoubleConeBackbone(int(observation_space.shape[0]), backbone_channels, pooled_channels,
+                                      init_layers_orthogonal=cnn_orth, in_num_res_blocks=in_num_res_blocks,
+                                      cone_num_res_blocks=cone_num_res_blocks, out_num_res_blocks=out_num_res_blocks,
+                                      gelu_pool_conv=gelu_pool_conv)
+        super().__init__(observation_space, action_space, action_plane_space, backbone, backbone_channels,
+                         num_additional_critics=num_additional_critics,
+                         additional_critic_activation_functions=additional_critic_activation_functions,
+                         critic_channels=critic_channels, init_layers_orthogonal=init_layers_orthogonal,
+                         cnn_layers_init_orthogonal=cnn_orth, output_activation_fn=output_activation_fn,
+                         subaction_mask=subaction_mask)

@@ -712,22 +712,45 @@ class ActorCritic(nn.Module):
                  decoder_residual_blocks_per_level=None, increment_kernel_size_on_down_conv=False,
                  output_activation_fn="identity", subaction_mask=None, critic_shares_backbone=None,
                  save_critic_separate=None, shared_critic_head=None, normalization=None,
-                 impala_channels=(16, 32, 32), **kwargs):
+                 impala_channels=(16, 32, 32), backbone_channels=128, pooled_channels=512, in_num_res_blocks=4,
+                 cone_num_res_blocks=6, out_num_res_blocks=4, gelu_pool_conv=True, **kwargs):
         super().__init__()
         assert use_sde or not squash_output, "squash_output only valid if use_sde"  # shared/actor/make_actor.py
         if not share_features_extractor:
             raise NotImplementedError("SeparateActorCriticNetwork is outside the hot-path scope")
-        if actor_head_style not in ("single", "squeeze_unet"):
+        if actor_head_style not in ("single", "squeeze_unet", "double_cone"):
             raise NotImplementedError(f"actor_head_style={actor_head_style} is outside the hot-path scope")
+        if actor_head_style == "double_cone" and normalization:  # actor_critic.py: not passed on to this network
+            raise NotImplementedError("normalization with actor_head_style=double_cone: the reference's "
+                                      "DoubleConeActorCritic takes none")
         self.env = env
         self.action_space = env.single_action_space
         self.observation_space = env.single_observation_space
         assert not use_sde or is_box(env.single_action_space), "use_sde only valid if Box action_space"
         self.squash_output = squash_output
-        self.gridnet = actor_head_style == "squeeze_unet"
+        self.gridnet = actor_head_style in ("squeeze_unet", "double_cone")
         if self.gridnet and use_sde:
-            raise NotImplementedError("use_sde with actor_head_style=squeeze_unet is outside the hot-path scope")
-        if self.gridnet:  # actor_critic.py:200-229 (MicroRTS, config C5)
+            raise NotImplementedError(f"use_sde with actor_head_style={actor_head_style} is outside the hot-path "
+                                      "scope")
+        if actor_head_style == "double_cone":  # actor_critic.py:173-193 (MicroRTS selfplay-dc, Lux)
+            from .backbone import DoubleConeActorCritic
+
+            plane = getattr(env, "action_plane_space", None)
+            assert plane is not None, "double_cone needs the env's action_plane_space"
+            if ((critic_shares_backbone is not None and not critic_shares_backbone) or save_critic_separate
+                    or shared_critic_head):
+                raise NotImplementedError("non-shared / shared-head critics are outside the hot-path scope")
+            self.network = DoubleConeActorCritic(
+                env.single_observation_space, env.single_action_space, plane,
+                init_layers_orthogonal=init_layers_orthogonal, cnn_layers_init_orthogonal=cnn_layers_init_orthogonal,
+                backbone_channels=backbone_channels, pooled_channels=pooled_channels,
+                critic_channels=critic_channels, in_num_res_blocks=in_num_res_blocks,
+                cone_num_res_blocks=cone_num_res_blocks, out_num_res_blocks=out_num_res_blocks,
+                num_additional_critics=num_additional_critics,
+                additional_critic_activation_functions=additional_critic_activation_functions,
+                gelu_pool_conv=gelu_pool_conv, output_activation_fn=output_activation_fn,
+                subaction_mask=subaction_mask)
+        elif self.gridnet:  # actor_critic.py:200-229 (MicroRTS, config C5)
             from .backbone import SqueezeUnetActorCriticNetwork
 
             plane = getattr(env, "action_plane_space", None)
