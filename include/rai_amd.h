@@ -1132,6 +1132,34 @@ int rai_md_sample(const float* logits, const uint8_t* mask, const int32_t* nvec,
                   uint64_t seed, uint64_t offset, int64_t* actions_out, float* logp_out, const float* v_in,
                   float* v_out, int32_t K, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Recorded-action ingest of the reference-AI rollout generator (csrc/ref_actions.hip).  Replaces the fold of
+ * vec_env.last_action into the action buffer, rl_algo_impls/rollout/reference_ai_rollout.py:69-70, for integer
+ * action spaces: GridNet (cells = map cells), flat MultiDiscrete and flat Discrete (cells = 1; Discrete: G = 1).
+ * src: (R, G) integers on the device, R = N * cells rows, int32 (src_dtype RAI_REF_ACT_I32) or int64
+ * (RAI_REF_ACT_I64).  nvec (G) is a HOST array read at call time, as for the heads; A = sum(nvec).
+ * mask (R, A) uint8, any byte alignment, or NULL (nothing is masked out).  dst (R, G) int64, 8-byte aligned:
+ * a slot of the (T, N, ...) action buffer.  bad (N) int32.  Per component (r, g) with value a:
+ *   a < 0 or a >= nvec[g], compared at the source's full width (an int64 whose low 32 bits look valid is
+ *     out of range): dst = 0, counted;
+ *   a in range, the group's mask slice has a true entry and mask[r, off_g + a] is false: dst = a, counted;
+ *   otherwise dst = a.
+ * bad[n] = the counted components of env n, written once by an ordinary store (no atomics, nothing to zero
+ * beforehand; two calls give the same bits).  One launch.
+ * A group whose mask slice is all false constrains nothing: the heads give such a group log-prob 0, entropy 0
+ * and no gradient whatever its action is (rai_gridnet_*, rai_md_head_*), so a recorded non-zero action there
+ * does not change the group's own loss term and is stored as it is.  It can still change the loss through a
+ * GridNet ValueDependentMask (sub_ref / sub_val): the gate of another group, and Batch.num_actions, read the
+ * recorded value of their reference group even where that group's own mask is all false.
+ * Errors, nothing launched: G outside [1, RAI_MD_MAX_G], an nvec entry < 1, cells < 1, an unknown src_dtype,
+ * N < 0: RAI_E_SHAPE; A > RAI_GRID_MAX_A (beyond the heads too): RAI_E_UNSUPPORTED; NULL nvec, or N > 0 with
+ * NULL src / dst / bad: RAI_E_NULLPTR.  N == 0: RAI_OK.
+ * ------------------------------------------------------------------------ */
+#define RAI_REF_ACT_I32 0
+#define RAI_REF_ACT_I64 1
+int rai_ref_actions_store(const void* src, int32_t src_dtype, const int32_t* nvec, int32_t G, const uint8_t* mask,
+                          int64_t N, int32_t cells, int64_t* dst, int32_t* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

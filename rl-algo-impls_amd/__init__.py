@@ -21,6 +21,7 @@ _LAZY = {
     "ReplayBufferRolloutGenerator": "replay",
     "ActorCritic": "policy",
     "SyncStepRolloutGenerator": "rollout",
+    "ReferenceAIRolloutGenerator": "reference_rollout",
     "DeviceRollout": "rollout",
     "Batch": "rollout",
     "TeacherKLLoss": "teacher_kl",

@@ -328,7 +328,9 @@ _SIGNATURES = {
     "rai_md_head_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rai_md_head_bwd": (C.c_int, [_vp] * 6 + [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "rai_md_sample": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _u64, _u64, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "rai_ref_actions_store": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
+RAI_REF_ACT_I32, RAI_REF_ACT_I64 = 0, 1
 RAI_DP_UID_BYTES = 128
 EXPORTED = tuple(_SIGNATURES)
 

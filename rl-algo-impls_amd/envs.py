@@ -300,3 +300,148 @@ class CartPoleVecEnv:
 
     def close(self):
         pass
+
+
+class ScriptedBotGridVecEnv:
+    """A MicroRTS-shaped vector env played by a scripted bot, for the reference-AI rollout generator
+    (reference_rollout.ReferenceAIRolloutGenerator): GridNet actions MultiDiscrete(tile(nvec, cells)) with
+    action_plane_space MultiDiscrete(nvec), get_action_mask() (N, cells, sum(nvec)) bool and last_action
+    (N, cells, len(nvec)) int32, the bot's action of the step just taken.
+
+    Observations f32 (N, PLANES, h, w) ~ U[0, 1) come from a pool of `obs_pool` batches drawn at construction
+    (a seeded pool index per step).  Masks and the bot are pure functions of the current observation:
+      mask_of(obs):  cell c is empty ("no unit": every entry false) when plane 0 is below 0.35; in a live cell
+                     entry a is valid when (floor(64 obs[1 + a % 5]) + a) % 3 != 0, and group
+                     d = floor(16 obs[6]) is all false when d < G (about 7 live cells in 16 have one);
+      bot_action(obs, mask): per group the k-th valid entry, k = floor(1024 obs[1 + g % 5]) mod the group's
+                     number of valid entries; 0 where the group has none.  Always legal.
+    step(actions) ignores `actions` for the dynamics and appends a copy of what it received to self.received.
+    With illegal_every = m > 0 the (step, env) pairs p = step * N + n with p % m == m - 1 get one in-range
+    but masked-out component: illegal_component(mask[n]) names it (the first group, in (cell, group) order,
+    that has both a valid and an invalid entry, set to its first invalid entry); a pair whose mask has no such
+    group is left alone.  Out-of-range values are never emitted.  Reward ~ U[0, 1) f32 (N,), termination
+    ~ Bernoulli(term_prob), both from the env's generator."""
+
+    PLANES = 7
+
+    def __init__(self, num_envs: int, map_hw=(4, 4), nvec=MICRORTS_NVEC, seed: int = 1, illegal_every: int = 0,
+                 term_prob: float = 1 / 8, obs_pool: int = 8):
+        self.num_envs = int(num_envs)
+        self.map_hw = tuple(int(x) for x in map_hw)
+        self.cells = self.map_hw[0] * self.map_hw[1]
+        self.nvec = np.asarray(nvec, dtype=np.int64)
+        self.illegal_every = int(illegal_every)
+        self.term_prob = term_prob
+        self.rng = np.random.default_rng(seed)
+        self._make_spaces()
+        self._pool = [self.rng.random((self.num_envs,) + self.single_observation_space.shape, dtype=np.float32)
+                      for _ in range(int(obs_pool))]
+        self.received: list = []
+        self.steps = 0
+        self._obs = self._pool[0]
+        self.last_action = np.zeros(self._action_shape(), dtype=np.int32)
+
+    def _make_spaces(self) -> None:
+        self.single_observation_space = Box(0.0, 1.0, (self.PLANES,) + self.map_hw, np.float32)
+        self.action_plane_space = MultiDiscrete(self.nvec)
+        self.single_action_space = MultiDiscrete(np.tile(self.nvec, self.cells))
+
+    def _action_shape(self) -> Tuple[int, ...]:
+        return (self.num_envs, self.cells, len(self.nvec))
+
+    def _mask_shape(self) -> Tuple[int, ...]:
+        return (self.num_envs, self.cells, int(self.nvec.sum()))
+
+    @property
+    def unwrapped(self):
+        return self
+
+    def _planes(self, obs: np.ndarray) -> np.ndarray:
+        """(N, cells, PLANES)"""
+        o = np.asarray(obs, dtype=np.float32).reshape(-1, self.PLANES, self.cells)
+        return np.moveaxis(o, 1, 2)
+
+    def mask_of(self, obs: np.ndarray) -> np.ndarray:
+        o = self._planes(obs)
+        A, G = int(self.nvec.sum()), len(self.nvec)
+        a = np.arange(A)
+        m = (np.floor(64.0 * o[:, :, 1 + a % 5]).astype(np.int64) + a) % 3 != 0
+        group_of = np.repeat(np.arange(G), self.nvec)
+        dead = np.floor(16.0 * o[:, :, 6]).astype(np.int64)
+        m &= group_of[None, None, :] != dead[:, :, None]
+        m &= (o[:, :, 0] >= np.float32(0.35))[:, :, None]
+        return m.reshape((o.shape[0],) + self._mask_shape()[1:])
+
+    def bot_action(self, obs: np.ndarray, mask: np.ndarray) -> np.ndarray:
+        o = self._planes(obs)
+        m = np.asarray(mask).reshape(o.shape[0], self.cells, -1)
+        out = np.zeros((o.shape[0], self.cells, len(self.nvec)), dtype=np.int32)
+        off = 0
+        for g, n in enumerate(self.nvec):
+            mg = m[:, :, off:off + int(n)]
+            cnt = mg.sum(-1)
+            k = np.floor(1024.0 * o[:, :, 1 + g % 5]).astype(np.int64) % np.maximum(cnt, 1)
+            pick = (np.cumsum(mg, -1) == (k + 1)[:, :, None]) & mg  # the k-th valid entry
+            out[:, :, g] = np.where(cnt > 0, pick.argmax(-1), 0)
+            off += int(n)
+        return out.reshape((o.shape[0],) + self._action_shape()[1:])
+
+    def illegal_component(self, mask_env: np.ndarray):
+        """(cell, group, value) of the component illegal_every corrupts for an env with this mask, or None."""
+        m = np.asarray(mask_env).reshape(self.cells, -1)
+        for c in range(self.cells):
+            off = 0
+            for g, n in enumerate(self.nvec):
+                mg = m[c, off:off + int(n)]
+                if mg.any() and not mg.all():
+                    return c, g, int(np.argmin(mg))
+                off += int(n)
+        return None
+
+    def get_action_mask(self) -> np.ndarray:
+        return self.mask_of(self._obs)
+
+    def reset(self, **kwargs) -> Tuple[np.ndarray, Dict[str, Any]]:
+        self._obs = self._pool[int(self.rng.integers(len(self._pool)))]
+        return self._obs, {}
+
+    def step(self, actions):
+        N = self.num_envs
+        self.received.append(np.array(actions, copy=True))
+        mask = self.get_action_mask()
+        act = self.bot_action(self._obs, mask).reshape(N, self.cells, len(self.nvec))
+        if self.illegal_every > 0:
+            for n in range(N):
+                if (self.steps * N + n) % self.illegal_every == self.illegal_every - 1:
+                    hit = self.illegal_component(mask[n])
+                    if hit is not None:
+                        act[n, hit[0], hit[1]] = hit[2]
+        self.last_action = act.reshape(self._action_shape())
+        self.steps += 1
+        self._obs = self._pool[int(self.rng.integers(len(self._pool)))]
+        rew = self.rng.random(N, dtype=np.float32)
+        term = self.rng.random(N) < self.term_prob
+        return self._obs, rew, term, np.zeros(N, dtype=np.bool_), {}
+
+    def close(self):
+        pass
+
+
+class ScriptedBotDiscreteVecEnv(ScriptedBotGridVecEnv):
+    """The flat sibling of ScriptedBotGridVecEnv: one cell, one group.  Observations (N, PLANES), a
+    Discrete(n) action space, get_action_mask() (N, n) and last_action (N,) int32, by the same functions."""
+
+    def __init__(self, num_envs: int, n: int = 6, seed: int = 1, illegal_every: int = 0, term_prob: float = 1 / 8,
+                 obs_pool: int = 8):
+        super().__init__(num_envs, map_hw=(1, 1), nvec=(n,), seed=seed, illegal_every=illegal_every,
+                         term_prob=term_prob, obs_pool=obs_pool)
+
+    def _make_spaces(self) -> None:
+        self.single_observation_space = Box(0.0, 1.0, (self.PLANES,), np.float32)
+        self.single_action_space = Discrete(int(self.nvec[0]))
+
+    def _action_shape(self) -> Tuple[int, ...]:
+        return (self.num_envs,)
+
+    def _mask_shape(self) -> Tuple[int, ...]:
+        return (self.num_envs, int(self.nvec[0]))

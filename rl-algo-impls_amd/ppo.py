@@ -160,6 +160,8 @@ class PPO(PPOEpochKernels, PPODataParallel):
             chart["teacher_kl_loss_coef"] = self.teacher_kl_loss_coef
         log_scalars(self.tb_writer, "charts", chart, timesteps_elapsed)
 
+        if self.world > 1 and not getattr(rollout_generator, "data_parallel", True):
+            raise NotImplementedError(f"{type(rollout_generator).__name__} under data parallel (world > 1)")
         r = rollout_generator.rollout(gamma=self.gamma, gae_lambda=self.gae_lambda)
         if self.teacher_kl_loss_fn:  # ppo.py:259-262
             r.add_to_batch(self.teacher_kl_loss_fn.add_to_batch, rollout_generator.vec_env.num_envs)

@@ -12,6 +12,7 @@ from .acbc import ACBC
 from .dqn import DQN, DQNPolicy
 from .policy import ActorCritic
 from .ppo import PPO
+from .reference_rollout import ReferenceAIRolloutGenerator
 from .replay import ReplayBufferRolloutGenerator
 from .rollout import SyncStepRolloutGenerator
 
@@ -21,3 +22,6 @@ ALL_ALGOS = {**ALGOS, **OFF_POLICY_ALGOS}
 POLICIES = {"ppo": ActorCritic, "a2c": ActorCritic, "acbc": ActorCritic, "dqn": DQNPolicy}
 DEFAULT_ROLLOUT_GENERATORS = {"ppo": SyncStepRolloutGenerator, "a2c": SyncStepRolloutGenerator,
                               "acbc": SyncStepRolloutGenerator, "dqn": ReplayBufferRolloutGenerator}
+# the keys of rl_algo_impls/runner/train.py's rollout_type switch that are built here (guided and
+# guided_random are not)
+ROLLOUT_GENERATORS = {"sync": SyncStepRolloutGenerator, "reference": ReferenceAIRolloutGenerator}

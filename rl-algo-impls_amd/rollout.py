@@ -111,6 +111,11 @@ class RolloutGenerator(ABC):
     def rollout(self, **kwargs) -> Rollout: ...
 
 
+def _pinned(t: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """A host staging buffer: pinned beside a GPU, plain on the CPU (ReferenceAIRolloutGenerator's host path)."""
+    return t.pin_memory() if device.type == "cuda" else t
+
+
 def _free_host_buffers(hosts: List[int]) -> None:
     for h in hosts:
         _lib.lib().rai_host_free(C.c_void_p(h))
@@ -432,7 +437,7 @@ class SyncStepRolloutGenerator(RolloutGenerator):
                 A = act_space.n if self.discrete else int(np.sum(act_space.nvec))
                 assert m0.shape == (N, A) and m0.dtype == np.bool_, f"flat action mask {m0.shape} {m0.dtype}"
             self.action_masks = torch.zeros((T,) + m0.shape, dtype=torch.bool, device=dev)
-            self.h_mask = torch.zeros(m0.shape, dtype=torch.bool).pin_memory()
+            self.h_mask = _pinned(torch.zeros(m0.shape, dtype=torch.bool), dev)
             self.next_masks_dev = torch.zeros(m0.shape, dtype=torch.bool, device=dev)
         self.logprobs = torch.zeros((T, N), dtype=torch.float32, device=dev)
         self.actions = torch.zeros((T, N) + self.act_shape, dtype=act_dtype, device=dev)
@@ -441,10 +446,10 @@ class SyncStepRolloutGenerator(RolloutGenerator):
             self.act_low = torch.as_tensor(np.asarray(act_space.low, np.float32), device=dev)
             self.act_high = torch.as_tensor(np.asarray(act_space.high, np.float32), device=dev)
         # pinned host staging (H2D obs/rewards/dones, D2H actions)
-        self.h_obs = torch.zeros((N,) + tuple(obs_space.shape), dtype=self.obs_dtype).pin_memory()
-        self.h_rew = torch.zeros((N,) + vshape, dtype=torch.float32).pin_memory()
-        self.h_done = torch.zeros((N,), dtype=torch.bool).pin_memory()
-        self.h_act = torch.zeros((N,) + self.act_shape, dtype=act_dtype).pin_memory()
+        self.h_obs = _pinned(torch.zeros((N,) + tuple(obs_space.shape), dtype=self.obs_dtype), dev)
+        self.h_rew = _pinned(torch.zeros((N,) + vshape, dtype=torch.float32), dev)
+        self.h_done = _pinned(torch.zeros((N,), dtype=torch.bool), dev)
+        self.h_act = _pinned(torch.zeros((N,) + self.act_shape, dtype=act_dtype), dev)
         self.next_obs_dev = torch.zeros((N,) + tuple(obs_space.shape), dtype=self.obs_dtype, device=dev)
         # finished episodes' returns / lengths (gymnasium RecordEpisodeStatistics convention
         # info["episode"], info["_episode"]; what EpisodeStatsWriter logs as train_rolling/*,
