@@ -238,7 +238,8 @@ int rai_bias_relu_bwd(const float* dy, const float* y, int64_t rows, int32_t C, 
  * out = relu(x + b) in the flattened NCHW order (B, C * HW) that nn.Flatten gives, the backward takes
  * dy and y in that order and writes dx in NHWC (B, HW, C) for the convolution's backward, with db as
  * rai_bias_relu_bwd (same workspace).  The two layout copies around the flatten disappear into the
- * passes.  (C + 1) * HW <= 8192, C % 4 == 0, C / 4 dividing 256; dx 16-B aligned. */
+ * passes.  (C + 1) * HW <= 8192, C % 4 == 0, C / 4 dividing 256; dx 16-B aligned.
+ * HW == 1 (a 1x1 plane, where the two orders coincide) is supported, for aligned and unaligned dy / y. */
 int rai_bias_relu_fwd_nchw(const float* x, const float* b, int64_t B, int32_t HW, int32_t C, float* out,
                            void* stream);
 int rai_bias_relu_bwd_nchw(const float* dy, const float* y, int64_t B, int32_t HW, int32_t C, float* dx, float* db,
@@ -628,7 +629,10 @@ int rai_gather_minibatch_next(rai_minibatch_desc* desc, int32_t n_fields, void* 
  * Backward, two launches: from the upstream d_logp, d_entropy, d_v (B): d_enc (B, D) written, and the
  * gradients of wpi (A, D), bpi (A), wv (D), bv (1) written (accumulate == 0) or added (accumulate != 0,
  * e.g. into the flat .grad buffer).  A in 2..10 or 12; workspace >= rai_categorical_critic_heads_
- * workspace_bytes(B, A).  Fixed reduction orders (deterministic). */
+ * workspace_bytes(B, A).  Fixed reduction orders (deterministic).
+ * B == 0: RAI_OK and nothing is launched.  rai_categorical_critic_heads_bwd then writes NOTHING: d_enc is
+ * empty and g_wpi, g_bpi, g_wv, g_bv keep what they held, with accumulate == 0 too (a caller that wants
+ * the empty batch's zero gradient there zeroes them itself); the arguments are still checked. */
 int rai_categorical_critic_heads_fwd(const float* enc, const float* wpi, const float* bpi, const float* wv,
                                      const float* bv, const int64_t* actions, int64_t B, int32_t D, int32_t A,
                                      float* logits_out, float* logp_out, float* entropy_out, float* v_out,
@@ -643,7 +647,9 @@ int rai_categorical_critic_heads_bwd(const float* enc, const float* wpi, const f
 /* The same backward with the ReLU backward of the layer that produced enc folded in (round 4; NatureCNN's
  * fc -> ReLU, rl_algo_impls/shared/encoder/cnn.py:44-53): dz = enc <= 0 ? 0 : d_enc (threshold_backward on
  * the saved ReLU output) is written in place of d_enc, and g_benc (D floats) receives that layer's bias
- * gradient (the column sums of dz, fixed order; accumulate != 0 adds).  Replaces rai_bias_relu_bwd there. */
+ * gradient (the column sums of dz, fixed order; accumulate != 0 adds).  Replaces rai_bias_relu_bwd there.
+ * B == 0: g_benc is zeroed when accumulate == 0 (as rai_bias_relu_bwd's db); the four head gradients
+ * are left as they are, as above. */
 int rai_categorical_critic_heads_bwd_relu(const float* enc, const float* wpi, const float* bpi, const float* wv,
                                           const float* bv, const int64_t* actions, const float* logits, int64_t B,
                                           int32_t D, int32_t A, const float* d_logp, const float* d_entropy,

@@ -368,6 +368,7 @@ __global__ __launch_bounds__(BR_THREADS) void bias_relu_fwd_nchw_kernel(const fl
 // VEC (round 4, 16-B aligned dy / y): the sample's NCHW plane is read as float4s, all of a thread's loads
 // issued before the first use (one memory round trip per sample instead of one per loop trip), and the
 // channel of element e is e * ceil(2^32 / HW) >> 32 (exact for e < 8192) instead of an integer division.
+// HW == 1 (a 1x1 plane: c = e) is taken apart: ceil(2^32 / 1) does not fit the 32-bit constant.
 template <bool VEC = false>
 __global__ __launch_bounds__(BR_THREADS) void bias_relu_bwd_nchw_kernel(const float* __restrict__ dy,
                                                                        const float* __restrict__ y, int64_t B, int HW,
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(BR_THREADS) void bias_relu_bwd_nchw_kernel(const fl
 #pragma unroll
           for (int q = 0; q < 4; ++q) {  // NCHW element e = c * HW + p
             const unsigned e = 4u * (unsigned)m4 + q;
-            const int c = (int)__umulhi(e, magic), p = (int)e - c * HW;
+            const int c = HW == 1 ? (int)e : (int)__umulhi(e, magic), p = (int)e - c * HW;
             t[p * ld + c] = yv[i][q] <= 0.f ? 0.f : gv[i][q];
           }
         }

@@ -42,16 +42,17 @@ def test_heads_match_module_path(B, D, A):
                                    err_msg=name)
 
     # in place: gradients added to existing .grad views (the trainer's flat buffer)
-    for p in params:
-        p.grad = torch.full_like(p, 0.25)
+    pre = [0.25 * torch.randn_like(p) for p in params]  # different per element: a gradient added at the wrong
+    for p, p0 in zip(params, pre):                      # index shows
+        p.grad = p0.clone()
     e3 = enc.clone().requires_grad_(True)
     with cnn_ops.direct_grads():
         out = cnn_ops.CategoricalCriticHeads.apply(e3, params[0], params[1], params[2], params[3], act)
     torch.autograd.backward(out, up)
     np.testing.assert_allclose(e3.grad.cpu().numpy(), gref[0].cpu().numpy(), rtol=2e-4,
                                atol=2e-5 * float(gref[0].abs().max()))
-    for p, b in zip(params, gref[1:]):
-        np.testing.assert_allclose((p.grad - 0.25).cpu().numpy(), b.reshape(p.shape).cpu().numpy(), rtol=2e-4,
+    for p, p0, b in zip(params, pre, gref[1:]):
+        np.testing.assert_allclose((p.grad - p0).cpu().numpy(), b.reshape(p.shape).cpu().numpy(), rtol=2e-4,
                                    atol=2e-5 * float(b.abs().max()) + 1e-6)
 
 
@@ -87,8 +88,9 @@ def test_fc_relu_heads_fold_matches_the_separate_nodes(B, A):
     ref = (d.log_prob(act), d.entropy(), v(enc))
     gref = torch.autograd.grad(ref, [x1] + params, up)
 
-    for p in params:
-        p.grad = torch.full_like(p, 0.25)
+    pre = [0.25 * torch.randn_like(p) for p in params]
+    for p, p0 in zip(params, pre):
+        p.grad = p0.clone()
     x2 = x.clone().requires_grad_(True)
     with cnn_ops.direct_grads():
         assert cnn_ops.fc_relu_heads_fusable(net, fc, x2, None)
@@ -98,8 +100,8 @@ def test_fc_relu_heads_fold_matches_the_separate_nodes(B, A):
     torch.autograd.backward(out, up)
     np.testing.assert_allclose(x2.grad.cpu().numpy(), gref[0].cpu().numpy(), rtol=2e-4,
                                atol=2e-5 * float(gref[0].abs().max()))
-    for name, p, b in zip(("w_fc", "b_fc", "wpi", "bpi", "wv", "bv"), params, gref[1:]):
-        np.testing.assert_allclose((p.grad - 0.25).cpu().numpy(), b.reshape(p.shape).cpu().numpy(), rtol=2e-4,
+    for name, p, p0, b in zip(("w_fc", "b_fc", "wpi", "bpi", "wv", "bv"), params, pre, gref[1:]):
+        np.testing.assert_allclose((p.grad - p0).cpu().numpy(), b.reshape(p.shape).cpu().numpy(), rtol=2e-4,
                                    atol=2e-5 * float(b.abs().max()) + 1e-6, err_msg=name)
     # outside direct_grads() the fold does not apply (autograd-returned gradients keep the separate nodes)
     assert not cnn_ops.fc_relu_heads_fusable(net, fc, x2, None)

@@ -649,18 +649,19 @@ def test_bias_relu_fwd_bwd_match_torch(rows, C):
     assert torch.equal(torch.nan_to_num(y), torch.nan_to_num(ref))
     y = torch.nan_to_num(y)
     ws = torch.zeros(int(L.rai_bias_relu_workspace_bytes(C)), dtype=torch.uint8, device=DEV)
+    pre = (0.5 * torch.randn(C, generator=g)).to(DEV)  # different per element: a sum added at the wrong index shows
     dbs = []
     for acc in (0, 1, 0):
         dx = torch.empty_like(x)
-        db = torch.full((C,), 0.5, device=DEV)
+        db = pre.clone()
         _lib.check(L.rai_bias_relu_bwd(dy.data_ptr(), y.data_ptr(), rows, C, dx.data_ptr(), db.data_ptr(), acc,
                                        ws.data_ptr(), ws.numel(), st), "bwd")
         dx_ref = torch.ops.aten.threshold_backward(dy, y, 0.0)
         assert torch.equal(dx, dx_ref)
         db_ref = dx_ref.double().sum(0)
-        np.testing.assert_allclose(db.double().cpu().numpy(), (db_ref + (0.5 if acc else 0.0)).cpu().numpy(),
-                                   rtol=1e-5, atol=2e-6 * rows ** 0.5)
-        dbs.append(db - (0.5 if acc else 0.0))
+        want = db_ref + (pre.double() if acc else 0.0)
+        np.testing.assert_allclose(db.double().cpu().numpy(), want.cpu().numpy(), rtol=1e-5, atol=2e-6 * rows ** 0.5)
+        dbs.append(db)
     assert torch.equal(dbs[0], dbs[2])  # deterministic
     assert bool((ws[-576:].view(torch.int32) == 0).all())  # the arrival counters, re-armed
 
@@ -683,17 +684,19 @@ def test_bias_relu_nchw_pair_matches_torch_flatten(B, H, W, C):
     dy = torch.randn(B, C * H * W, generator=g).to(DEV)
     ws = torch.zeros(int(L.rai_bias_relu_workspace_bytes(C)), dtype=torch.uint8, device=DEV)
     dx_ref = torch.ops.aten.threshold_backward(dy, y, 0.0).view(B, C, H, W)
+    pre = (0.5 * torch.randn(C, generator=g)).to(DEV)
     dbs = []
     for acc in (0, 1, 0):
         dx = torch.empty(B, C, H, W, device=DEV, memory_format=torch.channels_last)
-        db = torch.full((C,), 0.5, device=DEV)
+        db = pre.clone()
         _lib.check(L.rai_bias_relu_bwd_nchw(dy.data_ptr(), y.data_ptr(), B, H * W, C, dx.data_ptr(), db.data_ptr(),
                                             acc, ws.data_ptr(), ws.numel(), st), "bwd_nchw")
         assert torch.equal(dx, dx_ref)
         db_ref = dx_ref.double().sum((0, 2, 3))
-        np.testing.assert_allclose(db.double().cpu().numpy(), (db_ref + (0.5 if acc else 0.0)).cpu().numpy(),
-                                   rtol=1e-5, atol=2e-6 * (B * H * W) ** 0.5)
-        dbs.append(db - (0.5 if acc else 0.0))
+        want = db_ref + (pre.double() if acc else 0.0)
+        np.testing.assert_allclose(db.double().cpu().numpy(), want.cpu().numpy(), rtol=1e-5,
+                                   atol=2e-6 * (B * H * W) ** 0.5)
+        dbs.append(db)
     assert torch.equal(dbs[0], dbs[2])
     assert bool((ws[-576:].view(torch.int32) == 0).all())
     # the scalar form (RAI_BRT_VEC=0; also taken for misaligned dy / y) gives the same bits as the float4 form
